@@ -7,8 +7,27 @@ f64 arithmetic, f32 RGB + sRGB BGR written to HBM.  The scene is uploaded once
 (inputs resident in HBM before timing); output stays in HBM (the PCIe copy and
 the host gather are reported beside `value`, never in it).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...     (one process per GPU)
+
+A plain run does what the headline figure needs and no more: it sets up
+(context, scene upload, rt_ctx_reserve), renders W warmup frames, times K
+frames, writes the last timed frame's outputs when --dump-outputs is given,
+and prints the result line.  --full adds every other measurement to that line,
+each a run of its own after the timed region: the repeated upload, the first
+two frames' wall clock, the per-kernel-family launch times, the work-count
+frame (`compute`), the host frame gather, the PCIe-inclusive rt_render and the
+CPU baseline (--no-kernel-times, --no-gather, --no-pcie, --no-cpu drop single
+legs of it).
+
+--dump-outputs DIR writes what the timed path left in its output buffers after
+its last step, as float32 DIR/rgb.npy (the f32 colours) and DIR/bgr.npy (the
+sRGB bytes), one row per pixel.  A frame of more than 2^20 pixels is written
+as a fixed seeded sample of its pixels, whose flat indices (row * width +
+column within this process's rows) are DIR/pixel_index.npy (float64).  Scene,
+view and sample are seeded, so two runs with the same arguments render and
+write the same pixels.  With N > 1 ranks every rank writes its own rows, the
+file names ending in _rank<r>.
 
 Every N measures the headline config C3: the N = 1 line is the headline
 number, and N > 1 deals that same 4096² frame over the N GPUs (strong
@@ -30,7 +49,7 @@ BASELINE config 4's "image tiled across GPUs"; per-rank projection on one GPU:
 weak (opt-in) renders the same scene and view at sqrt(N) x the resolution,
 every rank a 4096^2-pixel share; its line names that larger frame in
 `metric`, never the headline's.
-After the timed region every rank renders its bands again, K frames, with
+With --full, after the timed region every rank renders its bands again, K frames, with
 rt_render straight into ONE shared page-locked host frame (the host gather of
 SURVEY §8(e), RT_OUT_FRAME_ROWS: the copies overlap the render), reported as
 `host_frame` beside the device-only value.  --config c4 / c5 select the larger configs of BASELINE.json;
@@ -82,6 +101,14 @@ def parse():
     p.add_argument("--spheres", type=int, default=0)
     p.add_argument("--depth", type=int, default=-1)
     p.add_argument("--algo", default="auto", choices=["auto", "wavefront", "lds", "global", "path"])
+    p.add_argument("--full", action="store_true",
+                   help="also measure what the headline figure does not need, each in runs of its own after the "
+                        "timed region: repeated upload, first-frame wall clock, per-kernel launch times, work "
+                        "counts, host gather, PCIe-inclusive render, CPU baseline")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write the last timed step's outputs as float32 DIR/rgb.npy and "
+                        "DIR/bgr.npy (a fixed seeded sample of the pixels, DIR/pixel_index.npy, when the frame "
+                        "has more than 2^20 of them)")
     p.add_argument("--cpu-seconds", type=float, default=20.0,
                    help="target CPU time of the cpu_baseline samples (split between 1 thread and all threads)")
     p.add_argument("--no-cpu", action="store_true")
@@ -250,6 +277,30 @@ def pmc_traffic(config_key, sources_id):
         return None, "tuning differs from the measured default schedule"
     return float(e["hbm_bytes_per_launch"]), (f"profiles/pmc_traffic.json[{config_key}]: rocprofv3 --pmc FETCH_SIZE x2 "
                                               f"+ WRITE_SIZE, one render, same sources ({sources_id})")
+
+
+DUMP_PIXELS = 1 << 20          # --dump-outputs: 2 x 12 B + 8 B per sampled pixel, 29 MB at most
+DUMP_SEED = 20240
+
+
+def dump_outputs(path, rgb, bgr, rank, world):
+    """--dump-outputs: this process's output buffers as the timed loop's last step left
+    them (rgb: rows x W x 3 f32, bgr: rows x 3W u8, both on the device), one row per
+    pixel, float32.  More than DUMP_PIXELS pixels: a fixed seeded sample of them (drawn
+    with replacement, duplicates dropped, ascending), its flat indices beside it."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    n = rgb.shape[0] * rgb.shape[1]
+    tag = f"_rank{rank}" if world > 1 else ""
+    rgb, bgr = rgb.reshape(n, 3), bgr.reshape(n, 3)
+    if n > DUMP_PIXELS:
+        idx = np.unique(np.random.default_rng(DUMP_SEED).integers(0, n, DUMP_PIXELS))
+        sel = torch.from_numpy(idx).to(rgb.device)
+        rgb, bgr = rgb.index_select(0, sel), bgr.index_select(0, sel)
+        np.save(os.path.join(path, f"pixel_index{tag}.npy"), idx.astype(np.float64))
+    np.save(os.path.join(path, f"rgb{tag}.npy"), rgb.cpu().numpy().astype(np.float32, copy=False))
+    np.save(os.path.join(path, f"bgr{tag}.npy"), bgr.cpu().numpy().astype(np.float32))
 
 
 class SharedFrame:
@@ -463,10 +514,11 @@ def main():
         c.upload(scene)
         torch.cuda.synchronize(dev)
         upload_ms.append((time.perf_counter() - t0u) * 1e3)
-    t0u = time.perf_counter()
-    ctxs[0].upload(scene)                  # again: the blob exists, so no allocation (a caller's scene change)
-    torch.cuda.synchronize(dev)
-    upload_ms.append((time.perf_counter() - t0u) * 1e3)
+    if args.full:
+        t0u = time.perf_counter()
+        ctxs[0].upload(scene)              # again: the blob exists, so no allocation (a caller's scene change)
+        torch.cuda.synchronize(dev)
+        upload_ms.append((time.perf_counter() - t0u) * 1e3)
     ctx = ctxs[0]
     rows = shard.local_rows(H, BAND, band_world, rank)
     algo = {"auto": lr.RT_ALGO_AUTO, "wavefront": lr.RT_ALGO_WAVEFRONT, "lds": lr.RT_ALGO_BRUTE_LDS,
@@ -499,13 +551,13 @@ def main():
         t0r = time.perf_counter()
         c.reserve(opts, stream_ptr=s_.cuda_stream)
         reserve_ms.append((time.perf_counter() - t0r) * 1e3)
-    # the first two frames after it, against each other: what a process that renders one frame (as
-    # main.rs does) pays for its render once ctx_create, the upload and the reserve are done
+    # --full: the first two frames after it, against each other: what a process that renders one frame
+    # (as main.rs does) pays for its render once ctx_create, the upload and the reserve are done
     cold_ms = []
     for i in range(max(args.warmup, F)):
         t0c = time.perf_counter()
         step(i=i)
-        if i < 2:
+        if args.full and i < 2:
             torch.cuda.synchronize(dev)
             cold_ms.append((time.perf_counter() - t0c) * 1e3)
     torch.cuda.synchronize(dev)
@@ -540,7 +592,11 @@ def main():
     elapsed = time.perf_counter() - t0
     kernel_ms = [a.elapsed_time(b) for a, b in evs] if F > 1 else [span[0].elapsed_time(span[1]) / args.steps]
     avg_kernel_ms = sum(kernel_ms) / len(kernel_ms)
-    if F > 1:
+    if args.dump_outputs:
+        # the buffers of the last timed step, before any later render writes them again
+        last = (args.steps - 1) % F
+        dump_outputs(args.dump_outputs, outs[last][0], outs[last][1], rank, world)
+    if F > 1 and args.full:
         # with frames in flight an event span covers other frames' work too: the roofline's
         # per-render duration comes from K more renders issued one at a time on one context
         evs1 = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
@@ -552,32 +608,36 @@ def main():
         kernel_ms = [a.elapsed_time(b) for a, b in evs1]
         avg_kernel_ms = sum(kernel_ms) / len(kernel_ms)
     ktimes = {}
-    if not args.no_kernel_times:
+    if args.full and not args.no_kernel_times:
         for _ in range(args.steps):
             step(opts_timed)
         torch.cuda.synchronize(dev)
         ktimes = ctx.kernel_times()        # {family: (ms summed over K instrumented frames, launches)}
 
-    # one more, untimed frame with the instrumented kernels: exact box / sphere test counts
-    work = lr.render_opts(W, H, flags=lr.RT_OUT_RGB_F32 | lr.RT_OUT_BGR_U8 | lr.RT_COUNT_WORK, **common)
-    ctx.render_device(work, out_rgb.data_ptr(), out_bgr.data_ptr(), stream.cuda_stream)
-    torch.cuda.synchronize(dev)
-    wst = ctx.stats()
-    try:
-        gen_q, gen_s = ctx.generation_counts()
-    except lr.RtError:
-        gen_q, gen_s = [], []
+    # --full: one more, untimed frame with the instrumented kernels: exact box / sphere test counts
+    sphere_tests = box_tests = 0
+    gen_q, gen_s = [], []
+    if args.full:
+        work = lr.render_opts(W, H, flags=lr.RT_OUT_RGB_F32 | lr.RT_OUT_BGR_U8 | lr.RT_COUNT_WORK, **common)
+        ctx.render_device(work, out_rgb.data_ptr(), out_bgr.data_ptr(), stream.cuda_stream)
+        torch.cuda.synchronize(dev)
+        wst = ctx.stats()
+        sphere_tests, box_tests = wst.sphere_tests, wst.box_tests
+        try:
+            gen_q, gen_s = ctx.generation_counts()
+        except lr.RtError:
+            pass
 
-    # the frame end to end: every rank's rt_render of its bands straight into one
-    # shared page-locked host frame, the gather overlapping the render (RT_OUT_FRAME_ROWS)
+    # --full: the frame end to end: every rank's rt_render of its bands straight into
+    # one shared page-locked host frame, the gather overlapping the render (RT_OUT_FRAME_ROWS)
     hframe = None
-    if not args.no_gather and not path_cfg:
+    if args.full and not args.no_gather and not path_cfg:
         hframe = frame_gather(dist, world, rank, ctx, lr, W, H, pitch, common, args.steps, red_dev)
 
-    # PCIe-inclusive rate: rt_render into reused pageable host buffers, kernels + D2H.
-    # Reported beside `value`, never as it.
+    # --full: PCIe-inclusive rate: rt_render into reused pageable host buffers, kernels +
+    # D2H.  Reported beside `value`, never as it.
     host = {}
-    if world == 1 and not args.no_pcie:
+    if args.full and world == 1 and not args.no_pcie:
         hb = np.zeros((len(rows), pitch), np.uint8)
         hr = np.zeros((len(rows), W, 3), np.float32)
         for name, out in (("bgr", (None, hb)), ("rgb_bgr", (hr, hb))):
@@ -594,7 +654,7 @@ def main():
             host[name + "_samples"] = [round(x, 3) for x in ms]
 
     n_gpus = distinct_devices()
-    t = torch.tensor([elapsed, float(local_rays), avg_kernel_ms, float(wst.sphere_tests), float(wst.box_tests),
+    t = torch.tensor([elapsed, float(local_rays), avg_kernel_ms, float(sphere_tests), float(box_tests),
                       float(local_traced)], dtype=torch.float64, device=red_dev)
     if world > 1:
         mx = t.clone()
@@ -606,7 +666,6 @@ def main():
         sphere_tests, box_tests = int(sm[3].item()), int(sm[4].item())
     else:
         total_rays, total_traced = local_rays, local_traced
-        sphere_tests, box_tests = wst.sphere_tests, wst.box_tests
 
     if rank == 0:
         ms_per_step = elapsed / args.steps * 1e3
@@ -680,6 +739,11 @@ def main():
                         "generation_queue_sizes": gen_q[:args.depth + 3] if world == 1 else None,
                         "generation_shaded": gen_s[:args.depth + 3] if world == 1 else None},
         }
+        if not args.full:
+            del line["compute"]            # the work counts come from a frame of their own
+            if F > 1:
+                del line["roofline"]       # its per-render duration needs renders issued one at a time
+        line["full"] = bool(args.full)
         if len(cold_ms) == 2:
             line["first_frame_ms"] = {"first": round(cold_ms[0], 3), "second": round(cold_ms[1], 3),
                                       "note": "wall clock of the first two renders after rt_scene_upload and "
@@ -688,7 +752,8 @@ def main():
                                               "and the kernels' code objects)"}
             line["first_frame_ms"]["reserve_ms"] = round(reserve_ms[0], 3)
             line["first_frame_ms"]["ctx_create_ms"] = round(create_ms, 3)
-        line["upload_ms"] = {"first": round(upload_ms[0], 3), "repeat": round(min(upload_ms[1:]), 3),
+        line["upload_ms"] = {"first": round(upload_ms[0], 3),
+                             "repeat": round(min(upload_ms[1:]), 3) if args.full else None,
                              "note": "rt_scene_upload once per scene, outside the timed region: host SAH BVH + "
                                      "4-wide tree + light-view grids + camera view, then one H2D copy of the blob"}
         if hframe is not None:
@@ -715,7 +780,7 @@ def main():
                         f"BGR (+ {W * H * 12 / 1e6:.0f} MB f32 RGB) through the pinned staging slices: the frame "
                         f"after the camera pass, during the later generations, then the packed segments of the "
                         f"chain pixels (tuning sparse_out, DESIGN.md §3.11)"}
-        if world == 1 and not args.no_cpu:
+        if args.full and world == 1 and not args.no_cpu:
             try:
                 draws = dict(jitter=1, seed=cfg[3], rng=1) if path_cfg else {}
                 line["cpu_baseline"] = cpu_baseline(spec, args, **draws)

@@ -93,6 +93,50 @@ def test_weak_dry_run_names_the_larger_frame():
     assert f"{d['frame'][0]}x{d['frame'][1]}" in d["metric"]
 
 
+def test_plain_run_is_the_default_and_full_is_opt_in(monkeypatch):
+    sys.path[:0] = [ROOT, os.path.join(ROOT, "rust-raytrace_amd")]
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 7, 2)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == "d"
+
+
+def test_dump_outputs_whole_frame_and_seeded_sample(tmp_path):
+    """--dump-outputs: float32 .npy files, one row per pixel; a frame of more than
+    DUMP_PIXELS pixels is written as the same sample of its pixels every time."""
+    sys.path[:0] = [ROOT, os.path.join(ROOT, "rust-raytrace_amd")]
+    import numpy as np
+    import torch
+    import bench
+    rows, W = 5, 7
+    rgb = torch.arange(rows * W * 3, dtype=torch.float32).reshape(rows, W, 3) / 8
+    bgr = (torch.arange(rows * W * 3) % 256).to(torch.uint8).reshape(rows, 3 * W)
+    bench.dump_outputs(str(tmp_path / "a"), rgb, bgr, 0, 1)
+    assert sorted(os.listdir(tmp_path / "a")) == ["bgr.npy", "rgb.npy"]
+    r, b = np.load(tmp_path / "a" / "rgb.npy"), np.load(tmp_path / "a" / "bgr.npy")
+    assert r.dtype == b.dtype == np.float32 and r.shape == b.shape == (rows * W, 3)
+    assert np.array_equal(r, rgb.reshape(-1, 3).numpy()) and np.array_equal(b, bgr.reshape(-1, 3).numpy())
+
+    rows, W = 3, bench.DUMP_PIXELS // 2                      # 1.5 x DUMP_PIXELS pixels: sampled
+    rgb = torch.arange(rows * W, dtype=torch.float32).reshape(rows, W, 1).expand(rows, W, 3).contiguous()
+    bgr = (torch.arange(rows * W * 3) % 251).to(torch.uint8).reshape(rows, 3 * W)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), rgb, bgr, 1, 2)
+    idx = np.load(tmp_path / "b" / "pixel_index_rank1.npy")
+    assert idx.dtype == np.float64 and 0 < len(idx) <= bench.DUMP_PIXELS
+    assert np.all(np.diff(idx) > 0) and idx[0] >= 0 and idx[-1] < rows * W
+    r, b = np.load(tmp_path / "b" / "rgb_rank1.npy"), np.load(tmp_path / "b" / "bgr_rank1.npy")
+    assert r.dtype == b.dtype == np.float32 and r.shape == b.shape == (len(idx), 3)
+    assert np.array_equal(r[:, 0], idx.astype(np.float32))   # pixel values are their own indices (< 2^24)
+    assert np.array_equal(b, bgr.reshape(-1, 3).numpy()[idx.astype(np.int64)])
+    for name in os.listdir(tmp_path / "b"):
+        assert np.array_equal(np.load(tmp_path / "b" / name), np.load(tmp_path / "c" / name)), name
+    assert sum(os.path.getsize(tmp_path / "b" / n) for n in os.listdir(tmp_path / "b")) <= 64 << 20
+
+
 def test_cpu_baseline_sample_is_bounded():
     sys.path[:0] = [ROOT, os.path.join(ROOT, "rust-raytrace_amd")]
     import bench

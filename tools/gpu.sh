@@ -25,7 +25,7 @@ cd "$(dirname "$0")/.."
 O=gpurun_out/${S:-s}
 mkdir -p "$O"
 export TMPDIR=/tmp
-QUIET="--no-gather"
+QUIET="--full --no-gather"   # every bench.py step measures the whole line (less the host gather), as the tools expect
 
 line() {  # ms_per_step and value of a bench log's JSON line
   python3 -c "import json,sys; d=json.loads([l for l in open(sys.argv[1]) if l.startswith('{')][-1]); print(d['ms_per_step'], 'ms', d['value'], d['unit'])" "$1"

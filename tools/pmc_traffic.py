@@ -1,6 +1,6 @@
 """HBM bytes per render from rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes.
 
-Each pass ran `bench.py --steps S --warmup W` (W + S uninstrumented renders,
+Each pass ran `bench.py --full --steps S --warmup W` (W + S uninstrumented renders,
 then one RT_COUNT_WORK render, then the PCIe-inclusive rt_render calls).
 Frames are split at the generation-0 wf_nearest launch; the last frame before
 the RT_COUNT_WORK render (a timed-loop frame) is used.
