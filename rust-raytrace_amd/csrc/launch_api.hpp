@@ -1,4 +1,4 @@
-// Host-side launchers of the kernels in trace_kernel.hip (called by rt_device.cpp).
+// Host-side launchers of the kernels in trace_kernel.hip (called by rt_render.cpp and rt_device.cpp).
 #pragma once
 #include <hip/hip_runtime.h>
 

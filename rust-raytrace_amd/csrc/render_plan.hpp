@@ -1,0 +1,130 @@
+// The schedule of a render as arithmetic on plain data: which algorithm and sphere
+// sources, how the streams are shaped, how a tile is cut into chunks and regions,
+// where the fused tail starts and how a lane's working set is laid out.  Pure
+// functions of the scene's facts, the tuning array, the CU count and the validated
+// options: no HIP, no rt_ctx, no I/O (the caller prints the verbose lines from
+// what is returned), so every decision can be checked without a GPU
+// (tests/native/plan_check.cpp).
+#pragma once
+
+#include <cstddef>
+#include <cstdint>
+
+#include "device_layout.hpp"
+#include "raytrace_amd.h"
+#include "tuning.hpp"
+
+namespace rtamd {
+
+// LDS per traversal workgroup for staged scene data (1024 threads, two resident per CU)
+constexpr size_t kLdsBudget = 72 * 1024;
+constexpr int kPlanMaxBStreams = 4;     // = launch_api.hpp kMaxBStreams (checked where both are seen)
+
+constexpr size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+// What the planner reads of an uploaded scene (filled from rt_ctx by the caller).
+struct SceneFacts {
+    int32_t n_spheres = 0, n_bvh = 0, n_bvh4 = 0, n_q4 = 0, n_lights = 0;
+    bool has_half = false;            // binary16 nodes were built (DevScene::bvh_h)
+    bool has_cgrid = false;           // the camera's view grid was built (DevScene::cgrid)
+    bool needs_path = false;          // a class only the path kernel implements
+    bool deep_bvh4 = false, short_stack = false, short_stack18 = false, q4_ok = false, all_lights_gridded = false;
+};
+
+// ---- algorithm ------------------------------------------------------------------------
+// RT_ALGO_AUTO resolved to path / wavefront / brute LDS / brute global.  Returns RT_OK, or the
+// status of a refusal with its text in *err.
+int plan_algo(const SceneFacts& sf, int algo, int jitter, uint32_t spp, int* mode, const char** err);
+
+// ---- sphere sources ---------------------------------------------------------------------
+// (nearest, occlusion) sphere sources of a wavefront render, see launch_api.hpp; pfx2 / pfxq: the
+// nodes of the binary / quantised tree a prefix source stages in LDS (DevScene::pfx2 / pfxq, which
+// the caller stores when sets_prefix: RT_ALGO_WAVEFRONT_BRUTE leaves them as they are).
+struct SourcePair {
+    int src = 0, src_occ = 0;
+    bool sets_prefix = false;
+    int32_t pfx2 = 0, pfxq = 0;
+};
+SourcePair plan_sources(const SceneFacts& sf, const int64_t* tune, int mode);
+
+// ---- streams ----------------------------------------------------------------------------
+struct StreamShape {
+    bool split = false;     // shadow + shading kernels on b streams of their own
+    int n_b = 1;            // that many
+    int cam = 0;            // generation 0: 0 per ray, 3 / 4 the camera's view grid (spheres in LDS / through L2)
+    int grid_occ = 0;       // shadow kernel without a tree walk: spheres from LDS (1) or HBM/L2 (2); 0: general
+    uint32_t wg_major = 1;  // chunk dealing
+    int mark_gen = 0;       // lanes: the next chunk starts after this generation
+};
+StreamShape plan_streams(const SceneFacts& sf, const int64_t* tune, int mode, int src, uint32_t max_depth);
+
+// ---- chunks -----------------------------------------------------------------------------
+// Working-set bytes per element (device_layout.hpp, WfBufs): written once, read by the budget
+// (wf_bytes_per_slot) and by the carve-up (wf_layout).
+constexpr uint64_t kWfQueueBytes = 2ull * 8 * 8;     // per queue entry: two queues of 8 8-byte fields
+constexpr uint64_t kWfRecBytes = 7 * 8 + 4 * 4;      // per queue entry and level: a shade record
+constexpr uint64_t kWfLevBytes = 4 * 8 + 4;          // per chain and level: local colour, Schlick factor, object
+constexpr uint64_t kWfTermBytes = 3 * 8 + 1;         // per chain: terminal colour, levels pushed
+constexpr uint64_t kWfCpixBytes = 4;                 // per queue entry: the chain's pixel
+constexpr uint64_t kWfPmapBytes = 4;                 // per chunk pixel: the pixel map
+constexpr uint64_t kWfCcolBytes = 16;                // per chain: the chain colours
+
+// Working-set bytes per pixel slot of a chunk (wf_layout's sections, per slot):
+// two queues, one shade-record array and one level array per lit generation,
+// terminals and level counts, the chain's pixel, the pixel map and the chain colours.
+constexpr uint64_t wf_bytes_per_slot(uint64_t levels) {
+    return kWfQueueBytes + levels * kWfRecBytes + levels * kWfLevBytes + kWfTermBytes + kWfCpixBytes + kWfPmapBytes +
+           kWfCcolBytes;
+}
+
+// The chunk cap in pixels: tuning chunk_pixels, else what `budget` bytes (all lanes) hold at `levels`.
+uint64_t plan_cap_px(const int64_t* tune, uint64_t budget, uint64_t levels);
+
+struct ChunkPlan {
+    uint32_t tile_w = 0, tile_h = 0;
+    uint32_t tiles_x = 0;             // 8x8 tiles per row
+    uint32_t chunk_rows = 0;          // rows of the largest chunk (a multiple of 8): what the working set is sized for
+    uint32_t n_chunks = 0;
+    uint32_t first_rows = 0;          // > 0: two chunks of first_rows and tile_h - first_rows rows (host_first)
+    int n_lanes = 1;
+    uint32_t row0(uint32_t ci) const { return first_rows ? (ci ? first_rows : 0u) : ci * chunk_rows; }
+    uint32_t nrows(uint32_t ci) const {
+        if (first_rows) return ci ? tile_h - first_rows : first_rows;
+        const uint32_t left = tile_h - ci * chunk_rows;
+        return chunk_rows < left ? chunk_rows : left;
+    }
+    uint32_t cap() const { return tile_w * chunk_rows; }      // pixel capacity of a lane's working set
+    uint64_t next_cap_px() const {                            // out of memory: half the pixels per chunk
+        const uint64_t h = static_cast<uint64_t>(chunk_rows) * tile_w / 2;
+        return h > 1 ? h : 1;
+    }
+};
+// One call per attempt of the render's out-of-memory retry (cap_px: plan_cap_px, then next_cap_px).
+// bands: the render is rt_render's into host memory (host_chunks / host_first apply).
+ChunkPlan plan_chunks(const int64_t* tune, uint64_t cap_px, uint32_t tile_w, uint32_t tile_h, bool bands);
+
+// ---- regions ----------------------------------------------------------------------------
+struct RegionPlan {
+    uint32_t slots = 0;               // generation-0 slots of the largest chunk (8x8 tiles)
+    uint32_t G = 1, R = 0;            // regions per queue, entries per region
+};
+RegionPlan plan_regions(const int64_t* tune, int n_cu, const ChunkPlan& cp);
+
+// ---- fused tail -------------------------------------------------------------------------
+// The generation the fused tail (wf_tail) starts at for chunks of `slots` generation-0 slots; 0: none.
+int plan_tail_fuse(const SceneFacts& sf, const int64_t* tune, int src, uint64_t slots, uint32_t max_depth);
+
+// ---- working-set layout -----------------------------------------------------------------
+// A lane's wavefront working set for chunks of up to `cap` pixels: every queue and shade-record
+// array is G regions of R entries; the shade records have one such array per lit generation
+// (`levels` = max_depth + 1).  Sections 256-byte aligned; the queues start at 0.
+struct WfLayout {
+    uint64_t qcap = 0;                // queue capacity G * R (>= generation-0 slots)
+    uint64_t capa = 0;                // qcap rounded up to 64: per-chain arrays (chain = generation-0 record entry)
+    uint64_t s_queue = 0, s_rec = 0, s_lev = 0, s_term = 0, s_reg = 0, s_cpix = 0, s_pmap = 0, s_ccol = 0;
+    uint64_t o_rec = 0, o_lev = 0, o_term = 0, o_rq = 0, o_rs = 0, o_cpix = 0, o_pmap = 0, o_ccol = 0;
+    uint64_t total = 0;
+};
+WfLayout wf_layout(uint32_t cap, uint32_t G, uint32_t R, uint32_t levels);
+
+}  // namespace rtamd

@@ -749,7 +749,7 @@ def test_host_chunks_overlap_copies_bit_identically(gpu_ctx):
 
 @pytest.mark.parametrize("scene", ["config3", "config2", "fresnel"])
 def test_sparse_host_copies_bit_identical(gpu_ctx, scene):
-    """rt_render into host memory with tuning sparse_out (rt_device.cpp
+    """rt_render into host memory with tuning sparse_out (rt_copy.cpp
     copy_sparse: the frame copied after the camera pass, then the packed
     segments of the chain pixels scattered into it): every byte and colour as
     the plain copy, into buffers holding garbage, for widths around the
