@@ -154,7 +154,29 @@ typedef struct {
     ref_counts cnt;
     rng_t rng;
     int keyed;              /* REF_RNG_KEYED */
+    int trig_ulps, trig_hashed;   /* ref_opts: 0 = libm's results untouched */
 } ctx_t;
+
+/* ref_opts.trig_ulps: the cos / sin / pow results of the material and camera code moved
+ * |k| representable values up or down -- the sign of k, or, hashed, a bit of a hash of the
+ * call's operands (and of which function it is) XOR the sign of k.  A pure function of
+ * the call either way, so the render does not depend on threads or tiles.  The tests take
+ * the images of a few k as the envelope of every correctly-rounded-to-a-few-ulp libm. */
+static double trig_nudge(const ctx_t* c, double r, double a, double b, uint64_t fn) {
+    int k = c->trig_ulps;
+    if (k == 0) return r;
+    int up = k > 0;
+    if (c->trig_hashed) {
+        uint64_t ab, bb;
+        memcpy(&ab, &a, 8); memcpy(&bb, &b, 8);
+        up ^= (int)(kmix(ab ^ kmix(bb + fn * 0x9E3779B97F4A7C15ull)) & 1u);
+    }
+    for (int n = k < 0 ? -k : k; n > 0; --n) r = nextafter(r, up ? INFINITY : -INFINITY);
+    return r;
+}
+static inline double m_cos(const ctx_t* c, double x) { return trig_nudge(c, cos(x), x, 0.0, 1); }
+static inline double m_sin(const ctx_t* c, double x) { return trig_nudge(c, sin(x), x, 0.0, 2); }
+static inline double m_pow(const ctx_t* c, double x, double y) { return trig_nudge(c, pow(x, y), x, y, 3); }
 
 /* A [0,1) draw: the next XorShift output, or the keyed draw (key, id). */
 static inline double draw_f64(ctx_t* c, uint64_t key, uint32_t id) {
@@ -245,7 +267,7 @@ static col shade(ctx_t* c, const ref_object* m, const hit_t* hit, const ray_t* r
                 res = cadd(res, cmul(cmul(cmulc(kd, lc), clamp_zero(dot(ldir, normal))), FRAC_1_PI_));
             if (specular)
                 res = cadd(res, cmul(cmulc(ks, lc),
-                                     pow(clamp_zero(dot(normal, normalize(vsub(ldir, ray->direction)))), m->exponent)));
+                                     m_pow(c, clamp_zero(dot(normal, normalize(vsub(ldir, ray->direction)))), m->exponent)));
         }
         if (specular) {
             v3 d = ray->direction;
@@ -273,14 +295,14 @@ static col shade(ctx_t* c, const ref_object* m, const hit_t* hit, const ray_t* r
                     res = cadd(res, cmul(cmul(cmulc(kd, lc), clamp_zero(dot(ldir, normal))), FRAC_1_PI_));
                 if (specular)
                     res = cadd(res, cmul(cmulc(ks, lc),
-                                         pow(clamp_zero(dot(normal, normalize(vsub(ldir, ray->direction)))), m->exponent)));
+                                         m_pow(c, clamp_zero(dot(normal, normalize(vsub(ldir, ray->direction)))), m->exponent)));
             }
             for (uint32_t si = 0; si < m->samples; ++si) {
                 double r1 = draw_f64(c, key, 128 + 2 * si) * 2.0 - 1.0;
                 double r2 = draw_f64(c, key, 129 + 2 * si) * (2.0 * PI_);
                 double sin_theta = 1.0 - r1 * r1;          /* quirk: no sqrt (raytrace.rs:103) */
                 double phi = r2;
-                double x = sin_theta * cos(phi), z = sin_theta * sin(phi);
+                double x = sin_theta * m_cos(c, phi), z = sin_theta * m_sin(c, phi);
                 v3 d0 = V(x, r1, z);
                 v3 dir = dot(d0, normal) >= 0.0 ? d0 : vneg(d0);
                 ray_t nr; nr.origin = vadd(pt, vmul(dir, EPS_OFFSET)); nr.direction = dir;
@@ -289,7 +311,7 @@ static col shade(ctx_t* c, const ref_object* m, const hit_t* hit, const ray_t* r
                 if (diffuse) res = cadd(res, cdiv(cmul(cmulc(kd, cl), dot(normal, dir)), fac));
                 if (specular)   /* quirk: `ray` here is the NEW ray, so dir - dir = 0 (raytrace.rs:108,115) */
                     res = cadd(res, cdiv(cmul(cmulc(ks, cl),
-                                              pow(clamp_zero(dot(normal, normalize(vsub(dir, nr.direction)))), m->exponent)), fac));
+                                              m_pow(c, clamp_zero(dot(normal, normalize(vsub(dir, nr.direction)))), m->exponent)), fac));
             }
         }
         return res;
@@ -318,7 +340,7 @@ static col shade(ctx_t* c, const ref_object* m, const hit_t* hit, const ray_t* r
                 res = cadd(res, cmul(cmul(cmulc(kd, lc), clamp_zero(dot(ldir, normal))), FRAC_1_PI_));
             if (specular)
                 res = cadd(res, cmul(cmul(cmulc(ks, lc), fresnel),
-                                     pow(clamp_zero(dot(normal, normalize(vsub(ldir, ray->direction)))), m->exponent)));
+                                     m_pow(c, clamp_zero(dot(normal, normalize(vsub(ldir, ray->direction)))), m->exponent)));
         }
         if (specular) {
             v3 d = ray->direction;
@@ -358,7 +380,7 @@ static col shade(ctx_t* c, const ref_object* m, const hit_t* hit, const ray_t* r
             if (in_shadow(c, pt, ldir, rng_, sq)) continue;
             col lc = cfrom3(L->color);
             res = cadd(res, cmul(cmul(cmulc(ks, lc), fresnel),
-                                 pow(clamp_zero(dot(normal, normalize(vsub(ldir, ray->direction)))), m->exponent)));
+                                 m_pow(c, clamp_zero(dot(normal, normalize(vsub(ldir, ray->direction)))), m->exponent)));
         }
         if (specular) {
             v3 rd = vsub(ray->direction, vmul(normal, 2.0 * ndv));
@@ -464,7 +486,7 @@ static ray_t camera_project(ctx_t* c, double px, double py, uint64_t key) {
     double theta = draw_f64(c, key, 0) * (2.0 * PI_);
     double r2 = c->keyed ? key_closed01(key, 1) : rng_closed01(&c->rng);
     double rad = sqrt(r2) * c->s->camera.aperture;
-    v3 orig = vadd(ip, mat_mul(c->cam_m, V(cos(theta) * rad, sin(theta) * rad, 0.0)));
+    v3 orig = vadd(ip, mat_mul(c->cam_m, V(m_cos(c, theta) * rad, m_sin(c, theta) * rad, 0.0)));
     r.origin = orig; r.direction = normalize(vsub(fp, orig));
     return r;
 }
@@ -544,6 +566,7 @@ static void* worker(void* arg) {
     ctx_t c; memset(&c, 0, sizeof c);
     c.s = s; c.max_depth = o->max_depth;
     c.keyed = o->rng == REF_RNG_KEYED;
+    c.trig_ulps = o->trig_ulps; c.trig_hashed = o->trig_hashed != 0;
     double cpos[3];
     ref_camera_build(&s->camera, cpos, c.cam_m);
     c.cam_pos = from3(cpos);

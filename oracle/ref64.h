@@ -105,6 +105,12 @@ typedef struct {
     uint32_t band, band_stride, band_phase;
     int32_t threads;         /* <=0: all online CPUs */
     int32_t rng;             /* REF_RNG_XORSHIFT / REF_RNG_KEYED */
+    /* Test knob: every cos, sin and pow result of the material and camera code (not the
+     * sRGB tables) is replaced by nextafter applied |trig_ulps| times: upward for k > 0,
+     * downward for k < 0; with trig_hashed the direction is a hash bit of the call's
+     * operand bits, flipped for k < 0.  0: the results are libm's, bit for bit. */
+    int32_t trig_ulps;
+    int32_t trig_hashed;
 } ref_opts;
 
 typedef struct {

@@ -501,6 +501,9 @@ int render_path(rt_ctx* c, const rt_render_opts* o, RenderReq req, RenderCall& r
     if (req.dry) return warm_streams(c, {st});
     if (const int rc = zero_counters(c, st); rc != RT_OK) return rc;
     const bool staged = path_lds_bytes(c->dsc, true) <= 48 * 1024;
+    if (c->t(kTuneVerbose))
+        std::fprintf(stderr, "rtamd: path G %u T %u staged %d npix %llu\n", G, T, staged ? 1 : 0,
+                     static_cast<unsigned long long>(npix));
     c->ev0_set = true;
     HIP_TRY(c, hipEventRecord(c->ev0, st));
     HIP_TRY(c, launch_path(c->dsc, rcall.fp, ps, staged, st));
