@@ -249,7 +249,9 @@ typedef struct {
     int32_t jitter;           /* rt_jitter */
     uint32_t flags;           /* rt_out_flags */
     int32_t algo;             /* rt_algo */
-    uint32_t bgr_pitch;       /* bytes per output BGR row; 0 -> 3*tile_w */
+    uint32_t bgr_pitch;       /* bytes per output BGR row; 0 -> 3*tile_w.  The bytes of a row past its
+                                 3*tile_w pixel bytes: rt_render writes them as zero (BMP row padding,
+                                 main.rs:42); rt_render_device leaves them as the caller's buffer has them */
     uint32_t _pad;
     uint64_t seed;            /* keyed RNG seed: every random draw is a function of (seed, pixel, AA sample,
                                  camera sample, path through the ray tree, draw id), so a frame is
@@ -301,6 +303,11 @@ int rt_render_device(rt_ctx* ctx, const rt_render_opts* opts, void* d_rgb, void*
  * rt_render_device calls will be issued on (its hardware queue is set up too;
  * NULL = the context's own stream, which rt_render uses). */
 int rt_ctx_reserve(rt_ctx* ctx, const rt_render_opts* opts, int host, void* stream);
+/* Statistics of the most recent render (a refused call is no render); synchronises
+ * with it.  They, and rt_ctx_generation_counts, stay readable, with the same
+ * values and as often as wanted, after rt_ctx_reserve (whatever it allocates
+ * or frees), rt_ctx_set_tuning (also of the keys that rebuild the streams) and
+ * rt_scene_upload of another scene: the next render replaces them, nothing else. */
 int rt_ctx_stats(rt_ctx* ctx, rt_stats* stats);
 /* Diagnostic (device): the sphere test's division t = x / (2a) (shapes.rs:68,75)
  * computed as the device computes it (the per-ray reciprocal of 2a finished with

@@ -179,6 +179,8 @@ struct FrameParams {
     uint32_t band, band_stride, band_phase;
     uint32_t max_depth, spp;
     uint32_t bgr_pitch;
+    uint32_t pad_end;               // bytes [3 * tile_w, pad_end) of every BGR row are written as zero: bgr_pitch for
+                                    //   rt_render's own frame (BMP row padding, main.rs:42), 3 * tile_w (none) for a caller's buffer
     uint32_t row0, rows;            // this launch covers local rows [row0, row0 + rows) of the tile
     float* out_rgb;                 // tile_h * tile_w * 3, may be null
     uint8_t* out_bgr;               // tile_h * bgr_pitch, may be null

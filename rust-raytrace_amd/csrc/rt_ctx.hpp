@@ -40,6 +40,10 @@ struct RenderReq {
     // frame (8-way C3 share 0.655-0.656 vs 0.659-0.662 ms, C3 2.800 vs 2.812 ms, same box)
     bool skip_ev0 = false;
     bool banded_copy = false;  // rt_render writes a row-banded tile (copy_engine -2)
+    // rt_render: the device frame is the context's, and its rows are copied to the host whole: their
+    // padding (bgr_pitch > 3 * tile_w) is written as zero (main.rs:42).  rt_render_device writes
+    // pixels only: the rest of a caller's rows is the caller's
+    bool zero_pad = false;
     // rt_ctx_reserve: every allocation and stream the render would make, then warm_streams
     // instead of the launches; counters and the last render's statistics are left alone
     bool dry = false;
@@ -99,7 +103,8 @@ struct rt_ctx {
     hipEvent_t fork = nullptr;
     bool wf_used = false;
     // a one-chunk wavefront render leaves its tally (ray counts, per-generation queue sizes) to
-    // the first rt_ctx_stats / rt_ctx_generation_counts after it (flush_tally): not on the chain
+    // the first rt_ctx_stats / rt_ctx_generation_counts after it (flush_tally): not on the chain.
+    // It points into a lane's working set: release_lane_memory settles it before that is freed.
     struct PendingTally {
         bool on = false;
         bool zero = false;                 // the render left the counters to be cleared before the tally
@@ -208,7 +213,8 @@ constexpr size_t kRuntimeHeadroom = 4ull << 30;
 // A no-op launch with private memory on every stream of `ss` (the code objects load, each
 // hardware queue and its scratch are set up), then wait for them.
 int warm_streams(rt_ctx* c, const std::vector<hipStream_t>& ss);
-// Free every lane (streams, events, working set) once its work is done.
+// Free every lane (streams, events, working set) once its work is done; a pending tally is
+// settled first (release_lane_memory).
 void drop_lanes(rt_ctx* c);
 int check_join_error(rt_ctx* c);
 

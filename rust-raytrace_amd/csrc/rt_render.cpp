@@ -53,15 +53,30 @@ int ensure_bstreams(rt_ctx* c, rt_ctx::Lane& M, int nb) {
     return RT_OK;
 }
 
+int flush_tally(rt_ctx* c);
+
 // Release a lane's working set once the lane's own streams are idle: the only place lane
 // memory is freed.  Called by
 //   - drop_lanes (rt_ctx_destroy; rt_ctx_set_tuning when cu_mask, prio or a_queue changes),
 //   - ensure_wf, before it allocates a larger working set (after the pending render's end),
 //   - ensure_wavefront, for every lane, before a render retries with smaller chunks.
-void release_lane_memory(rt_ctx::Lane& L) {
+// A tally still pending (c->tally.on: a one-chunk render whose statistics nobody has read yet)
+// holds pointers into a working set, so it is settled first: run now, on the context's stream,
+// and waited for.  The counters then hold that render's totals and a later rt_ctx_stats /
+// rt_ctx_generation_counts only reads them.  (rt_ctx_destroy drops the tally before it gets here.)
+void release_lane_memory(rt_ctx* c, rt_ctx::Lane& L) {
     if (L.s) (void)hipStreamSynchronize(L.s);
     for (hipStream_t x : L.sb) if (x) (void)hipStreamSynchronize(x);
-    if (L.mem) (void)hipFree(L.mem);
+    if (!L.mem) return;
+    const bool settled = c->tally.on;
+    if (settled) {
+        (void)flush_tally(c);              // clears tally.on whatever it returns
+        (void)hipStreamSynchronize(c->stream);
+    }
+    if (c->t(kTuneVerbose))
+        std::fprintf(stderr, "rtamd: lane working set released (%llu MB), tally settled %d\n",
+                     static_cast<unsigned long long>(L.bytes >> 20), settled ? 1 : 0);
+    (void)hipFree(L.mem);
     L.mem = nullptr;
     L.bytes = 0;
 }
@@ -120,7 +135,7 @@ int ensure_wf(rt_ctx* c, rt_ctx::Lane& L, uint32_t cap, uint32_t G, uint32_t R, 
         if (L.mem) {
             // every render still using it is done (its chain may have run on a caller's stream)
             if (c->render_pending) (void)hipEventSynchronize(c->render_done);
-            release_lane_memory(L);
+            release_lane_memory(c, L);
         }
         // ask only for what the device has free, less the runtime's scratch headroom: a request
         // beyond it is answered without hipMalloc (the runtime has crashed inside a failing
@@ -215,6 +230,7 @@ int begin_render(rt_ctx* c, const rt_render_opts* o, void* d_rgb, void* d_bgr, v
     fp.max_depth = o->max_depth;
     fp.spp = spp;
     fp.bgr_pitch = pitch;
+    fp.pad_end = 3 * o->tile_w;
     fp.out_rgb = (o->flags & RT_OUT_RGB_F32) ? static_cast<float*>(d_rgb) : nullptr;
     fp.out_bgr = (o->flags & RT_OUT_BGR_U8) ? static_cast<uint8_t*>(d_bgr) : nullptr;
     fp.counters = c->d_counters;
@@ -284,7 +300,7 @@ int ensure_wavefront(rt_ctx* c, const rt_render_opts* o, RenderReq req, uint64_t
         }
         if (rc == RT_OK) return RT_OK;
         if (rc != RT_E_NOMEM || p.cp.chunk_rows <= 8) return rc;
-        for (auto& L : c->lanes) release_lane_memory(L);      // retry with half the pixels per chunk
+        for (auto& L : c->lanes) release_lane_memory(c, L);     // retry with half the pixels per chunk
         cap_px = p.cp.next_cap_px();
     }
 }
@@ -525,6 +541,7 @@ int render_device(rt_ctx* c, const rt_render_opts* o, void* d_rgb, void* d_bgr, 
     int rc = begin_render(c, o, d_rgb, d_bgr, stream, rcall);
     if (rc != RT_OK) return rc;
     const hipStream_t st = rcall.st;
+    if (req.zero_pad) rcall.fp.pad_end = rcall.fp.bgr_pitch;
     const SceneFacts sf = scene_facts(c);
     int mode = o->algo;
     const char* refusal = nullptr;
@@ -588,6 +605,7 @@ int host_request(rt_ctx* c, const rt_render_opts* o, bool rgb, bool bgr, bool dr
         return rc;
     h.req = RenderReq{};
     h.req.bands = true;
+    h.req.zero_pad = true;
     h.req.sparse = c->t(kTuneSparseOut) != 0;
     h.req.banded_copy = stride > 1;
     h.req.dry = dry;
@@ -666,7 +684,7 @@ int warm_streams(rt_ctx* c, const std::vector<hipStream_t>& ss) {
 
 void drop_lanes(rt_ctx* c) {
     for (auto& L : c->lanes) {
-        release_lane_memory(L);
+        release_lane_memory(c, L);
         if (L.mark) (void)hipEventDestroy(L.mark);
         if (L.done) (void)hipEventDestroy(L.done);
         for (hipEvent_t e : L.b_done) if (e) (void)hipEventDestroy(e);

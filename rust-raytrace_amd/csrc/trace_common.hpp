@@ -1367,7 +1367,7 @@ __device__ __forceinline__ void write_pixel(const FrameParams& fp, uint32_t lx, 
         q[1] = to_srgb(res.g, srgb);
         q[2] = to_srgb(res.r, srgb);
         if (lx == fp.tile_w - 1)       // BMP row padding is zero (main.rs:42)
-            for (uint32_t k = 3u * fp.tile_w; k < fp.bgr_pitch; ++k)
+            for (uint32_t k = 3u * fp.tile_w; k < fp.pad_end; ++k)
                 fp.out_bgr[static_cast<size_t>(out_row) * fp.bgr_pitch + k] = 0;
     }
 }

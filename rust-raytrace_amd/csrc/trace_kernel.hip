@@ -536,7 +536,7 @@ __device__ __forceinline__ void write_background_pixel(const FrameParams& fp, co
         uint8_t* q = fp.out_bgr + static_cast<size_t>(row) * fp.bgr_pitch + 3u * lx;
         q[0] = fp.bg_bgr[0]; q[1] = fp.bg_bgr[1]; q[2] = fp.bg_bgr[2];
         if (lx == fp.tile_w - 1)       // BMP row padding is zero (main.rs:42)
-            for (uint32_t k = 3u * fp.tile_w; k < fp.bgr_pitch; ++k) fp.out_bgr[static_cast<size_t>(row) * fp.bgr_pitch + k] = 0;
+            for (uint32_t k = 3u * fp.tile_w; k < fp.pad_end; ++k) fp.out_bgr[static_cast<size_t>(row) * fp.bgr_pitch + k] = 0;
     }
 }
 
@@ -1193,7 +1193,8 @@ __global__ __launch_bounds__(kWfThreads) void wf_compose(DevScene sc, FrameParam
     const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
     const uint32_t segs = (fp.tile_w + 63u) / 64u;                    // 64-pixel segments per row
     const uint64_t total = static_cast<uint64_t>(segs) * fp.rows;
-    const bool dw = ((fp.bgr_pitch | reinterpret_cast<uintptr_t>(fp.out_bgr)) & 3u) == 0;   // dword-aligned BGR rows
+    // dword-aligned BGR rows whose last dword the render may write whole (pixels, then zero padding)
+    const bool dw = ((fp.bgr_pitch | reinterpret_cast<uintptr_t>(fp.out_bgr)) & 3u) == 0 && ((3 * fp.tile_w + 3) & ~3u) <= fp.pad_end;
     for (uint64_t sg = static_cast<uint64_t>(blockIdx.x) * kComposeWaves + wave; sg < total;
          sg += static_cast<uint64_t>(gridDim.x) * kComposeWaves) {     // wave-uniform
         const uint32_t lrow = static_cast<uint32_t>(sg / segs), x0 = static_cast<uint32_t>(sg % segs) * 64u;
@@ -1251,7 +1252,7 @@ __global__ __launch_bounds__(kWfThreads) void wf_compose(DevScene sc, FrameParam
                 row[3 * x + 2] = static_cast<uint8_t>(q >> 16);
             }
             if (x0 + nv == fp.tile_w)                                  // BMP row padding is zero (main.rs:42)
-                for (uint32_t k = (dw ? (3 * fp.tile_w + 3) & ~3u : 3 * fp.tile_w) + lane; k < fp.bgr_pitch; k += 64)
+                for (uint32_t k = (dw ? (3 * fp.tile_w + 3) & ~3u : 3 * fp.tile_w) + lane; k < fp.pad_end; k += 64)
                     row[k] = 0;
         }
         __builtin_amdgcn_wave_barrier();
