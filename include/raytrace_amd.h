@@ -54,7 +54,9 @@
 extern "C" {
 #endif
 
-/* 5: rt_out_flags gained RT_OUT_FRAME_ROWS (rt_render writes a banded tile
+/* 6: rt_algo gained RT_ALGO_WAVEFRONT_AA (one wavefront pass per jittered AA sample); tuning key
+ * aa_wavefront added.  No struct changed.
+ * 5: rt_out_flags gained RT_OUT_FRAME_ROWS (rt_render writes a banded tile
  * straight into its rows of a whole-frame host buffer); rt_ctx_reserve added;
  * rt_sqrt_check added; rt_kernel_family index 6 is RT_KF_COMPOSE (earlier ABI-4 builds named it
  * RT_KF_SHADOW); the tuning keys fuse, lists,
@@ -67,7 +69,7 @@ extern "C" {
  * 4: rt_abi_version() added; RT_KF_TAIL (RT_KF_COUNT 8).  A caller checks
  * rt_abi_version() == RT_ABI_VERSION of the header it was built against before
  * passing any struct; any change of a struct, enum value or tuning key bumps it. */
-#define RT_ABI_VERSION 5
+#define RT_ABI_VERSION 6
 
 enum rt_status {
     RT_OK = 0,
@@ -234,9 +236,16 @@ enum rt_algo {
     RT_ALGO_BRUTE_GLOBAL = 2,   /* megakernel, sphere list read through the caches */
     RT_ALGO_WAVEFRONT = 3,      /* per-depth launches over compacted ray queues, sphere BVH (default) */
     RT_ALGO_WAVEFRONT_BRUTE = 4, /* the same schedule, every sphere tested (linear scan like scene.rs:248) */
-    RT_ALGO_PATH = 5            /* per-pixel recursion over an HBM stack: every material / light / camera class
+    RT_ALGO_PATH = 5,           /* per-pixel recursion over an HBM stack: every material / light / camera class
                                    (IndirectPhong, Transparent, AreaLight, DepthOfField, random jitter); AUTO picks
                                    it whenever the scene or the jitter mode needs it */
+    RT_ALGO_WAVEFRONT_AA = 6    /* RT_ALGO_WAVEFRONT's schedule run once per AA sample (main.rs:47-56): every sample
+                                   of a pixel gets its own jitter (rt_jitter, any spp >= 1) and its own ray tree;
+                                   the samples are summed in f64 in sample order and divided by spp, bit for bit
+                                   what RT_ALGO_PATH renders.  With RT_JITTER_CENTER or spp 1 it is
+                                   RT_ALGO_WAVEFRONT's render.  A scene that needs RT_ALGO_PATH (IndirectPhong,
+                                   Transparent, AreaLight, DepthOfField) or has more than 32 lights ->
+                                   RT_E_UNSUPPORTED.  AUTO picks it only under tuning aa_wavefront. */
 };
 
 typedef struct {
@@ -275,7 +284,8 @@ typedef struct {
     uint64_t traced_rays;     /* queries the device actually traced: `rays` / spp when a chain schedule
                                  renders spp identical centre-jitter samples once, else `rays` */
     uint64_t chunks;          /* row chunks the wavefront schedule ran the tile as (sized to the
-                                 working-set budget, tuning wf_budget_mb); 0 for other schedules */
+                                 working-set budget, tuning wf_budget_mb; RT_ALGO_WAVEFRONT_AA runs spp
+                                 passes per chunk and counts the chunk once); 0 for other schedules */
 } rt_stats;
 
 void rt_render_opts_default(rt_render_opts* o, uint32_t width, uint32_t height);
@@ -320,7 +330,7 @@ int rt_div_a2_check(rt_ctx* ctx, const double* x, const double* a, uint32_t n, d
  * DESIGN.md §4) -> fast[i], and the device's own sqrt -> slow[i].  Tests compare
  * both with IEEE sqrt bit for bit.  Synchronous. */
 int rt_sqrt_check(rt_ctx* ctx, const double* x, uint32_t n, double* fast, double* slow);
-/* Queue sizes of the last wavefront chunk: queue[k] = rays traced at depth k
+/* Queue sizes of the last wavefront chunk (RT_ALGO_WAVEFRONT_AA: of its last pass): queue[k] = rays traced at depth k
  * (generation 0: 0, the camera rays are not queued), shaded[k] = hits that
  * issued shadow queries.  Diagnostic. */
 int rt_ctx_generation_counts(rt_ctx* ctx, uint32_t* queue, uint32_t* shaded, int n);
@@ -335,7 +345,8 @@ enum rt_kernel_family {
     RT_KF_FOLD = 3,         /* wf_fold */
     RT_KF_TALLY = 4,        /* wf_tally */
     RT_KF_CAMERA = 5,       /* wf_nearest, generation 0 (camera rays) */
-    RT_KF_COMPOSE = 6,      /* wf_compose: the row-ordered frame pass (tuning compose) */
+    RT_KF_COMPOSE = 6,      /* wf_compose: the row-ordered frame pass (tuning compose); RT_ALGO_WAVEFRONT_AA:
+                               wf_resolve after a chunk's last pass (and wf_aa_compose per pass, tuning compose) */
     RT_KF_TAIL = 7,         /* wf_tail: the fused generations >= tail_fuse */
     RT_KF_COUNT = 8
 };
@@ -382,7 +393,9 @@ int rt_ctx_kernel_times(rt_ctx* ctx, double* ms, uint32_t* launches, int n);
  * after their work; 0: through events; a join that waits 2 s gives up and
  * makes the next rt_render or rt_ctx_stats fail; the default is 0 in a process whose
  * kernels are serialised, ROCPROF_COUNTER_COLLECTION or AMD_SERIALIZE_KERNEL
- * set, where the b streams could not run beside the join).
+ * set, where the b streams could not run beside the join), aa_wavefront (1:
+ * RT_ALGO_AUTO renders a scene of the chain classes with at most 32 lights, random
+ * jitter and spp > 1 as RT_ALGO_WAVEFRONT_AA instead of RT_ALGO_PATH; default 0).
  * cu_mask, prio and a_queue rebuild the context's streams (after pending work) when changed.
  * Unknown key or value out of range -> RT_E_INVALID.  Results never depend on
  * them (tests/test_gpu_parity.py renders under several and compares bits). */

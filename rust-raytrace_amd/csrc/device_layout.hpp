@@ -191,7 +191,18 @@ struct FrameParams {
     uint64_t seed;                  // keyed RNG seed (path kernel)
     const double* srgb;             // the 255 sRGB thresholds in HBM (path kernel stages them in LDS)
     uint32_t path_group;            // path kernel: lanes per pixel (power of two <= 64), sharing its AA samples
+    // RT_ALGO_WAVEFRONT_AA (one chain pass per AA sample).  aa_acc null: every other
+    // render (aa_pass 0: the camera rays are sample 0's).  A pass runs with spp = 1 (its tally counts
+    // the pass's own rays) and finishes a pixel by adding the pass's sample colour to aa_acc.
+    uint32_t aa_pass;               // the AA sample this pass traces (camera_ray's jitter key)
+    uint32_t aa_spp;                // the render's samples per pixel (wf_resolve divides by it)
+    uint32_t aa_flags;              // kAaTallyGens
+    double* aa_acc;                 // per chunk pixel p: the f64 running sum r, g, b at [3p, 3p + 3) (a lane's
+                                    //   working set, WfLayout::o_acc); pass 0 stores 0.0 + s_0, pass a adds s_a
+    double aa_bg[3];                // one sample's colour of a camera ray that misses: (0.0 + background) / 1.0
 };
+constexpr uint32_t kAaTallyGens = 1u;   // FrameParams::aa_flags: this pass's queue sizes go to gen_totals (the last
+                                        //   pass of the last chunk; rays and shadow rays are tallied every pass)
 
 
 

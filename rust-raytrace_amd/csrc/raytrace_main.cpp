@@ -9,7 +9,7 @@
 //
 //   raytrace [--scene FILE] [--out FILE] [--width W] [--height H] [--spp N]
 //            [--max-depth D] [--gpus N] [--band ROWS] [--jitter random|center] [--seed N]
-//            [--algo auto|wavefront|path|lds|global]
+//            [--algo auto|wavefront|wavefront-aa|path|lds|global]
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -53,11 +53,12 @@ bool parse_args(int argc, char** argv, Args& a) {
         else if (k == "--algo" && (v = val())) {
             std::string s = v;
             a.algo = s == "lds" ? RT_ALGO_BRUTE_LDS : s == "global" ? RT_ALGO_BRUTE_GLOBAL
-                   : s == "wavefront" ? RT_ALGO_WAVEFRONT : s == "path" ? RT_ALGO_PATH : RT_ALGO_AUTO;
+                   : s == "wavefront" ? RT_ALGO_WAVEFRONT : s == "wavefront-aa" ? RT_ALGO_WAVEFRONT_AA
+                   : s == "path" ? RT_ALGO_PATH : RT_ALGO_AUTO;
         } else {
             std::fprintf(stderr, "usage: raytrace [--scene FILE] [--out FILE] [--width W] [--height H] [--spp N]\n"
                                  "                [--max-depth D] [--gpus N] [--band ROWS] [--jitter random|center]\n"
-                                 "                [--seed N] [--algo auto|wavefront|path|lds|global]\n");
+                                 "                [--seed N] [--algo auto|wavefront|wavefront-aa|path|lds|global]\n");
             return false;
         }
     }

@@ -6,10 +6,27 @@
 
 namespace rtamd {
 
-int plan_algo(const SceneFacts& sf, int algo, int jitter, uint32_t spp, int* mode, const char** err) {
+int plan_algo(const SceneFacts& sf, int algo, int jitter, uint32_t spp, int* mode, const char** err, int aa_wavefront) {
     const size_t lds_bytes = static_cast<size_t>(sf.n_spheres) * sizeof(DevSphere);
     const bool fits_lds = lds_bytes <= 64 * 1024;
     int m = algo;
+    // one chain pass per AA sample (RT_ALGO_WAVEFRONT_AA): asked for, or AUTO's choice under tuning
+    // aa_wavefront for what only the path kernel renders otherwise (random jitter, spp > 1)
+    if (m == RT_ALGO_AUTO && aa_wavefront != 0 && !sf.needs_path && sf.n_lights <= 32 && jitter != RT_JITTER_CENTER && spp > 1)
+        m = RT_ALGO_WAVEFRONT_AA;
+    if (m == RT_ALGO_WAVEFRONT_AA) {
+        *mode = m;
+        if (sf.needs_path) {
+            *err = "RT_ALGO_WAVEFRONT_AA renders chain scenes only: IndirectPhong / Transparent materials, AreaLight and "
+                   "DepthOfFieldCamera need RT_ALGO_PATH";
+            return RT_E_UNSUPPORTED;
+        }
+        if (sf.n_lights > 32) {
+            *err = "RT_ALGO_WAVEFRONT_AA handles at most 32 lights (the wavefront path's limit); use RT_ALGO_PATH";
+            return RT_E_UNSUPPORTED;
+        }
+        return RT_OK;
+    }
     // the stochastic / branching classes, and random jitter with several AA
     // samples per pixel, run on the path kernel only (the chain schedules trace
     // one camera ray per pixel: centre jitter, or random jitter with spp = 1)
@@ -135,10 +152,10 @@ StreamShape plan_streams(const SceneFacts& sf, const int64_t* tune, int mode, in
     return s;
 }
 
-uint64_t plan_cap_px(const int64_t* tune, uint64_t budget, uint64_t levels) {
+uint64_t plan_cap_px(const int64_t* tune, uint64_t budget, uint64_t levels, bool aa) {
     const uint64_t cap_px = static_cast<uint64_t>(tune[kTuneChunkPixels]);
     if (cap_px != 0) return cap_px;
-    return std::max<uint64_t>(1, budget / static_cast<uint64_t>(tune[kTuneLanes]) / wf_bytes_per_slot(levels));
+    return std::max<uint64_t>(1, budget / static_cast<uint64_t>(tune[kTuneLanes]) / wf_bytes_per_slot(levels, aa));
 }
 
 // Chunks of whole rows, multiples of 8 (the generation-0 8x8 tiles), sized so
@@ -221,7 +238,7 @@ int plan_tail_fuse(const SceneFacts& sf, const int64_t* tune, int src, uint64_t 
     return ok ? T : 0;
 }
 
-WfLayout wf_layout(uint32_t cap, uint32_t G, uint32_t R, uint32_t levels) {
+WfLayout wf_layout(uint32_t cap, uint32_t G, uint32_t R, uint32_t levels, bool aa) {
     WfLayout w;
     const uint64_t q = static_cast<uint64_t>(G) * R;
     const uint64_t capa = align_up(q, 64);
@@ -236,6 +253,7 @@ WfLayout wf_layout(uint32_t cap, uint32_t G, uint32_t R, uint32_t levels) {
     w.s_cpix = q * kWfCpixBytes;
     w.s_pmap = static_cast<uint64_t>(cap) * kWfPmapBytes;
     w.s_ccol = capa * kWfCcolBytes;
+    w.s_acc = aa ? static_cast<uint64_t>(cap) * kWfAccBytes : 0;
     uint64_t off = align_up(w.s_queue, 256);
     w.o_rec = off; off = align_up(off + w.s_rec, 256);
     w.o_lev = off; off = align_up(off + w.s_lev, 256);
@@ -245,6 +263,7 @@ WfLayout wf_layout(uint32_t cap, uint32_t G, uint32_t R, uint32_t levels) {
     w.o_cpix = off; off = align_up(off + w.s_cpix, 256);
     w.o_pmap = off; off = align_up(off + w.s_pmap, 256);
     w.o_ccol = off; off = align_up(off + w.s_ccol, 256);
+    w.o_acc = off; off = align_up(off + w.s_acc, 256);
     w.total = off;
     return w;
 }

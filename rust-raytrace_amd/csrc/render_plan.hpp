@@ -32,9 +32,15 @@ struct SceneFacts {
 };
 
 // ---- algorithm ------------------------------------------------------------------------
-// RT_ALGO_AUTO resolved to path / wavefront / brute LDS / brute global.  Returns RT_OK, or the
-// status of a refusal with its text in *err.
-int plan_algo(const SceneFacts& sf, int algo, int jitter, uint32_t spp, int* mode, const char** err);
+// RT_ALGO_AUTO resolved to path / wavefront / brute LDS / brute global, or, with aa_wavefront
+// (the tuning key) set, to RT_ALGO_WAVEFRONT_AA for a chain-class scene of <= 32 lights rendered
+// with random jitter and spp > 1.  Returns RT_OK, or the status of a refusal with its text in *err.
+int plan_algo(const SceneFacts& sf, int algo, int jitter, uint32_t spp, int* mode, const char** err, int aa_wavefront = 0);
+// Whether a render of `mode` runs one chain pass per AA sample: RT_ALGO_WAVEFRONT_AA with random
+// jitter and spp > 1 (with centre jitter or one sample it is RT_ALGO_WAVEFRONT's render).
+inline bool plan_aa_passes(int mode, int jitter, uint32_t spp) {
+    return mode == RT_ALGO_WAVEFRONT_AA && jitter != RT_JITTER_CENTER && spp > 1;
+}
 
 // ---- sphere sources ---------------------------------------------------------------------
 // (nearest, occlusion) sphere sources of a wavefront render, see launch_api.hpp; pfx2 / pfxq: the
@@ -68,17 +74,19 @@ constexpr uint64_t kWfTermBytes = 3 * 8 + 1;         // per chain: terminal colo
 constexpr uint64_t kWfCpixBytes = 4;                 // per queue entry: the chain's pixel
 constexpr uint64_t kWfPmapBytes = 4;                 // per chunk pixel: the pixel map
 constexpr uint64_t kWfCcolBytes = 16;                // per chain: the chain colours
+constexpr uint64_t kWfAccBytes = 3 * 8;              // per chunk pixel, AA passes only: the f64 running sum
 
 // Working-set bytes per pixel slot of a chunk (wf_layout's sections, per slot):
 // two queues, one shade-record array and one level array per lit generation,
-// terminals and level counts, the chain's pixel, the pixel map and the chain colours.
-constexpr uint64_t wf_bytes_per_slot(uint64_t levels) {
+// terminals and level counts, the chain's pixel, the pixel map and the chain colours; aa (a render
+// of one pass per AA sample): also the running sums.
+constexpr uint64_t wf_bytes_per_slot(uint64_t levels, bool aa = false) {
     return kWfQueueBytes + levels * kWfRecBytes + levels * kWfLevBytes + kWfTermBytes + kWfCpixBytes + kWfPmapBytes +
-           kWfCcolBytes;
+           kWfCcolBytes + (aa ? kWfAccBytes : 0);
 }
 
 // The chunk cap in pixels: tuning chunk_pixels, else what `budget` bytes (all lanes) hold at `levels`.
-uint64_t plan_cap_px(const int64_t* tune, uint64_t budget, uint64_t levels);
+uint64_t plan_cap_px(const int64_t* tune, uint64_t budget, uint64_t levels, bool aa = false);
 
 struct ChunkPlan {
     uint32_t tile_w = 0, tile_h = 0;
@@ -117,14 +125,15 @@ int plan_tail_fuse(const SceneFacts& sf, const int64_t* tune, int src, uint64_t 
 // ---- working-set layout -----------------------------------------------------------------
 // A lane's wavefront working set for chunks of up to `cap` pixels: every queue and shade-record
 // array is G regions of R entries; the shade records have one such array per lit generation
-// (`levels` = max_depth + 1).  Sections 256-byte aligned; the queues start at 0.
+// (`levels` = max_depth + 1); aa: also the running sums of a render of one pass per AA sample
+// (3 f64 per chunk pixel, the last section).  Sections 256-byte aligned; the queues start at 0.
 struct WfLayout {
     uint64_t qcap = 0;                // queue capacity G * R (>= generation-0 slots)
     uint64_t capa = 0;                // qcap rounded up to 64: per-chain arrays (chain = generation-0 record entry)
-    uint64_t s_queue = 0, s_rec = 0, s_lev = 0, s_term = 0, s_reg = 0, s_cpix = 0, s_pmap = 0, s_ccol = 0;
-    uint64_t o_rec = 0, o_lev = 0, o_term = 0, o_rq = 0, o_rs = 0, o_cpix = 0, o_pmap = 0, o_ccol = 0;
+    uint64_t s_queue = 0, s_rec = 0, s_lev = 0, s_term = 0, s_reg = 0, s_cpix = 0, s_pmap = 0, s_ccol = 0, s_acc = 0;
+    uint64_t o_rec = 0, o_lev = 0, o_term = 0, o_rq = 0, o_rs = 0, o_cpix = 0, o_pmap = 0, o_ccol = 0, o_acc = 0;
     uint64_t total = 0;
 };
-WfLayout wf_layout(uint32_t cap, uint32_t G, uint32_t R, uint32_t levels);
+WfLayout wf_layout(uint32_t cap, uint32_t G, uint32_t R, uint32_t levels, bool aa = false);
 
 }  // namespace rtamd

@@ -90,6 +90,7 @@ struct rt_ctx {
         void* mem = nullptr;
         size_t bytes = 0;
         rtamd::WfBufs b{};
+        double* acc = nullptr;             // RT_ALGO_WAVEFRONT_AA: the chunk pixels' running sums, in mem (else null)
         uint64_t* dj = nullptr;            // device-side join flags (kDjWords words, zeroed once)
         uint64_t dj_n = 0;                 // the last join number handed out on them
         uint64_t* dj_err = nullptr;        // page-locked: a join gave up (host address; dj_err_dev the device's)

@@ -125,9 +125,9 @@ int ensure_lanes(rt_ctx* c, int n) {
 
 // A lane's wavefront working set for chunks of up to `cap` pixels, laid out by wf_layout and
 // grown on demand.
-int ensure_wf(rt_ctx* c, rt_ctx::Lane& L, uint32_t cap, uint32_t G, uint32_t R, uint32_t levels) {
+int ensure_wf(rt_ctx* c, rt_ctx::Lane& L, uint32_t cap, uint32_t G, uint32_t R, uint32_t levels, bool aa) {
     WfBufs& b = L.b;
-    const WfLayout w = wf_layout(cap, G, R, levels);
+    const WfLayout w = wf_layout(cap, G, R, levels, aa);
     b.o_rec = w.o_rec; b.o_lev = w.o_lev; b.o_term = w.o_term; b.o_rq = w.o_rq; b.o_rs = w.o_rs;
     b.o_cpix = w.o_cpix; b.o_pmap = w.o_pmap; b.o_ccol = w.o_ccol;
     const uint64_t off = w.total;
@@ -165,8 +165,12 @@ int ensure_wf(rt_ctx* c, rt_ctx::Lane& L, uint32_t cap, uint32_t G, uint32_t R, 
         }
         if (e != hipSuccess) return hip_fail(c, e, "hipMalloc(wavefront working set)");
         L.bytes = off;
+        if (c->t(kTuneVerbose))
+            std::fprintf(stderr, "rtamd: lane working set grown to %llu KB\n", static_cast<unsigned long long>(off >> 10));
     }
     b.mem = static_cast<unsigned char*>(L.mem);
+    // the running sums of a render of one pass per AA sample (the layout's last section)
+    L.acc = aa ? reinterpret_cast<double*>(static_cast<unsigned char*>(L.mem) + w.o_acc) : nullptr;
     b.totals = c->d_counters + kTotals;
     b.gen_totals = c->d_counters + kGenTotals;
     b.qcap = w.qcap;
@@ -196,7 +200,7 @@ int check_opts(rt_ctx* c, const rt_render_opts* o, uint32_t& spp, uint32_t& band
     if (spp == 0) return fail(c, RT_E_INVALID, "spp is 0 and the scene's antialias is 0");
     pitch = o->bgr_pitch ? o->bgr_pitch : 3 * o->tile_w;
     if (pitch < 3 * o->tile_w) return fail(c, RT_E_INVALID, "bgr_pitch < 3*tile_w");
-    if (o->algo < RT_ALGO_AUTO || o->algo > RT_ALGO_PATH) return fail(c, RT_E_INVALID, "bad algo");
+    if (o->algo < RT_ALGO_AUTO || o->algo > RT_ALGO_WAVEFRONT_AA) return fail(c, RT_E_INVALID, "bad algo");
     return RT_OK;
 }
 
@@ -277,6 +281,7 @@ int zero_counters(rt_ctx* c, hipStream_t st) {
 
 // The schedule of one wavefront render (render_plan.hpp).
 struct WfPlan {
+    bool aa = false;                   // one pass per AA sample (RT_ALGO_WAVEFRONT_AA, random jitter, spp > 1)
     SourcePair sp;
     StreamShape sh;
     ChunkPlan cp;
@@ -296,7 +301,7 @@ int ensure_wavefront(rt_ctx* c, const rt_render_opts* o, RenderReq req, uint64_t
         p.rg = plan_regions(c->tune, c->n_cu, p.cp);
         for (int l = 0; l < p.cp.n_lanes && rc == RT_OK; ++l) {
             if (p.sh.split && (rc = ensure_bstreams(c, c->lanes[l], p.sh.n_b)) != RT_OK) return rc;
-            rc = ensure_wf(c, c->lanes[l], p.cp.cap(), p.rg.G, p.rg.R, levels);
+            rc = ensure_wf(c, c->lanes[l], p.cp.cap(), p.rg.G, p.rg.R, levels, p.aa);
         }
         if (rc == RT_OK) return RT_OK;
         if (rc != RT_E_NOMEM || p.cp.chunk_rows <= 8) return rc;
@@ -376,7 +381,8 @@ int launch_chunks(rt_ctx* c, const rt_render_opts* o, RenderReq req, const Rende
     WfRun run;
     run.st = st;
     run.count = (o->flags & RT_COUNT_WORK) != 0;
-    run.lazy_tally = p.cp.n_chunks == 1 && n_lanes == 1;
+    // (a render of several passes tallies each pass as it ends: the next pass reuses the queue sizes)
+    run.lazy_tally = p.cp.n_chunks == 1 && n_lanes == 1 && !p.aa;
     if (!run.lazy_tally || run.count)
         if (const int rc = zero_counters(c, st); rc != RT_OK) return rc;
     // per-launch timing needs one in-order stream
@@ -415,7 +421,20 @@ int launch_chunks(rt_ctx* c, const rt_render_opts* o, RenderReq req, const Rende
             c->tally.n_lights = c->dsc.n_lights;
             c->tally.gens = static_cast<int>(o->max_depth) + 2;
         }
-        HIP_TRY(c, launch_wavefront(c->dsc, f, b, p.sp.src, p.sp.src_occ, run.count, ws, L.mark, p.sh.mark_gen));
+        // RT_ALGO_WAVEFRONT_AA: the chunk's passes back to back on its lane (stream order and the
+        // passes' own joins order a pixel's samples); the last one resolves the chunk's rows, and
+        // only it records the lane's mark and the chunk's band event
+        const uint32_t passes = p.aa ? f.aa_spp : 1u;
+        for (uint32_t a = 0; a < passes; ++a) {
+            const bool last = a + 1 == passes;
+            f.aa_pass = a;
+            f.aa_acc = p.aa ? L.acc : nullptr;
+            f.aa_flags = p.aa && last && ci + 1 == p.cp.n_chunks ? kAaTallyGens : 0u;
+            WfStreams wp = ws;
+            if (!last) wp.fold_ev = nullptr;
+            HIP_TRY(c, launch_wavefront(c->dsc, f, b, p.sp.src, p.sp.src_occ, run.count, wp, last ? L.mark : nullptr,
+                                        p.sh.mark_gen));
+        }
     }
     for (int l = 0; l < n_lanes && !run.on_caller; ++l) {
         HIP_TRY(c, hipEventRecord(c->lanes[l].done, c->lanes[l].s));
@@ -428,9 +447,10 @@ int launch_chunks(rt_ctx* c, const rt_render_opts* o, RenderReq req, const Rende
 // RT_ALGO_WAVEFRONT / RT_ALGO_WAVEFRONT_BRUTE: plan, make sure of lanes, streams and working
 // sets, then the dry warm-up (rt_ctx_reserve) or the launches.
 int render_wavefront(rt_ctx* c, const rt_render_opts* o, RenderReq req, const RenderCall& rcall, const SceneFacts& sf,
-                     int mode) {
+                     int mode, bool aa) {
     const FrameParams& fp = rcall.fp;
     WfPlan p;
+    p.aa = aa;
     p.sp = plan_sources(sf, c->tune, mode);
     if (p.sp.sets_prefix) {
         c->dsc.pfx2 = p.sp.pfx2;
@@ -446,13 +466,14 @@ int render_wavefront(rt_ctx* c, const rt_render_opts* o, RenderReq req, const Re
     uint64_t budget = 0;
     if (c->t(kTuneChunkPixels) == 0)
         budget = c->t(kTuneWfBudgetMb) > 0 ? static_cast<uint64_t>(c->t(kTuneWfBudgetMb)) << 20 : default_wf_budget(c);
-    int rc = ensure_wavefront(c, o, req, plan_cap_px(c->tune, budget, o->max_depth + 1ull), p);
+    int rc = ensure_wavefront(c, o, req, plan_cap_px(c->tune, budget, o->max_depth + 1ull, aa), p);
     if (rc != RT_OK) return rc;
     p.tail_fuse = plan_tail_fuse(sf, c->tune, p.sp.src, static_cast<uint64_t>(p.cp.tiles_x) * 64u * (p.cp.chunk_rows / 8),
                                  o->max_depth);
     // sparse host copies: a whole tile (contiguous rows or row bands) in one chunk on one lane,
     // pixels written where they end
-    c->sparse_on = req.sparse && p.cp.n_chunks == 1 && p.cp.n_lanes == 1 && c->t(kTuneCompose) == 0 &&
+    // (not for passes per AA sample: no pixel is final before the chunk's resolve)
+    c->sparse_on = req.sparse && !aa && p.cp.n_chunks == 1 && p.cp.n_lanes == 1 && c->t(kTuneCompose) == 0 &&
                    (fp.out_rgb || fp.out_bgr);
     if (c->sparse_on) {
         bool ok = false;
@@ -484,6 +505,9 @@ int render_wavefront(rt_ctx* c, const rt_render_opts* o, RenderReq req, const Re
     if (c->t(kTuneVerbose))
         std::fprintf(stderr, "rtamd: chunks %u x %u rows (first %u), lanes %d, G %u, R %u\n", p.cp.n_chunks, p.cp.chunk_rows,
                      p.cp.first_rows, p.cp.n_lanes, p.rg.G, p.rg.R);
+    if (aa && c->t(kTuneVerbose))
+        std::fprintf(stderr, "rtamd: aa passes %u, chunks %u x %u rows, resolve after each chunk's last pass, sums %s\n",
+                     fp.aa_spp, p.cp.n_chunks, p.cp.chunk_rows, c->t(kTuneCompose) ? "row by row (compose)" : "per pixel");
     return launch_chunks(c, o, req, rcall, p);
 }
 
@@ -545,7 +569,18 @@ int render_device(rt_ctx* c, const rt_render_opts* o, void* d_rgb, void* d_bgr, 
     const SceneFacts sf = scene_facts(c);
     int mode = o->algo;
     const char* refusal = nullptr;
-    if ((rc = plan_algo(sf, o->algo, o->jitter, rcall.spp, &mode, &refusal)) != RT_OK) return fail(c, rc, refusal);
+    if ((rc = plan_algo(sf, o->algo, o->jitter, rcall.spp, &mode, &refusal, static_cast<int>(c->t(kTuneAaWavefront)))) != RT_OK)
+        return fail(c, rc, refusal);
+    // RT_ALGO_WAVEFRONT_AA: one pass of RT_ALGO_WAVEFRONT's schedule per AA sample, each a render of
+    // one sample per pixel (its tally counts its own rays) that adds to the pixels' running sums;
+    // with centre jitter or one sample it is RT_ALGO_WAVEFRONT's render
+    const bool aa = plan_aa_passes(mode, o->jitter, rcall.spp);
+    if (mode == RT_ALGO_WAVEFRONT_AA) mode = RT_ALGO_WAVEFRONT;
+    if (aa) {
+        rcall.fp.aa_spp = rcall.spp;
+        rcall.fp.spp = 1;
+        for (int k = 0; k < 3; ++k) rcall.fp.aa_bg[k] = (0.0 + c->dsc.bg[k]) / 1.0;   // raytrace.rs:270-276, one camera sample
+    }
     if (!req.dry) {
         c->tally.on = false;
         c->last_pixels = static_cast<uint64_t>(o->tile_w) * o->tile_h;
@@ -561,13 +596,14 @@ int render_device(rt_ctx* c, const rt_render_opts* o, void* d_rgb, void* d_bgr, 
         if ((rc = zero_counters(c, st)) != RT_OK) return rc;
         return end_render(c, st, false);
     }
-    if (mode == RT_ALGO_WAVEFRONT || mode == RT_ALGO_WAVEFRONT_BRUTE) rc = render_wavefront(c, o, req, rcall, sf, mode);
+    if (mode == RT_ALGO_WAVEFRONT || mode == RT_ALGO_WAVEFRONT_BRUTE) rc = render_wavefront(c, o, req, rcall, sf, mode, aa);
     else if (mode == RT_ALGO_PATH) rc = render_path(c, o, req, rcall);
     else rc = render_brute(c, req, rcall, mode);
     if (rc != RT_OK || req.dry) return rc;
     // the chain schedules (wavefront, megakernel) trace one camera ray tree per
     // pixel and count it spp times: the spp centre-jitter samples are identical
-    if (mode != RT_ALGO_PATH) c->last_spp_traced = rcall.spp;
+    // (not the passes per AA sample: every sample is traced)
+    if (mode != RT_ALGO_PATH && !aa) c->last_spp_traced = rcall.spp;
     return end_render(c, st, true);
 }
 

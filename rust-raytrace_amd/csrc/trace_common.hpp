@@ -1306,15 +1306,16 @@ __device__ __forceinline__ void add_light(Col& res, const DevMaterial& m, const 
     }
 }
 
-// Pixel -> camera ray (main.rs:50-53; camera.rs:78) of AA sample 0: the
-// centre jitter, or the keyed draws of the pixel's first sample (fp.jitter;
-// the chain schedules take random jitter only with one sample per pixel).
-__device__ __forceinline__ Ray camera_ray(const DevScene& sc, const FrameParams& fp, uint32_t lx, uint32_t local_row) {
+// Pixel -> camera ray (main.rs:50-53; camera.rs:78) of AA sample `sample`: the
+// centre jitter, or the keyed draws of that sample (fp.jitter; the chain
+// schedules trace sample 0, RT_ALGO_WAVEFRONT_AA sample fp.aa_pass per pass).
+__device__ __forceinline__ Ray camera_ray(const DevScene& sc, const FrameParams& fp, uint32_t lx, uint32_t local_row,
+                                          uint32_t sample) {
     const uint32_t x = fp.x0 + lx;
     const uint32_t y = fp.y0 + ((local_row / fp.band) * fp.band_stride + fp.band_phase) * fp.band + local_row % fp.band;
     double jx = 0.5, jy = 0.5;
     if (fp.jitter) {
-        const uint64_t ka = key_child(key_pixel(fp.seed, x, y), 0);
+        const uint64_t ka = key_child(key_pixel(fp.seed, x, y), sample);
         jx = key_f64(ka, 0);
         jy = key_f64(ka, 1);
     }

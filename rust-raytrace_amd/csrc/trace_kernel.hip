@@ -131,7 +131,7 @@ __global__ __launch_bounds__(kBlock) void trace_frame_kernel(DevScene sc, FrameP
     const uint32_t ly = blockIdx.y * 16u + (wave >> 1) * 8u + (lane >> 3);
     uint32_t rays = 0, shadows = 0;
     if (lx < fp.tile_w && ly < fp.rows) {
-        const Ray cam = camera_ray(sc, fp, lx, fp.row0 + ly);
+        const Ray cam = camera_ray(sc, fp, lx, fp.row0 + ly, 0u);
         Col c;
         if constexpr (kLds) c = trace_chain(sc, static_cast<const DevSphere*>(lds_spheres), cam, fp.max_depth, rays, shadows);
         else c = trace_chain(sc, sc.spheres, cam, fp.max_depth, rays, shadows);
@@ -550,11 +550,32 @@ __device__ __forceinline__ Col end_colour(const DevScene& sc, int32_t obj) {
 
 typedef uint32_t U32x4 __attribute__((ext_vector_type(4)));
 
+// RT_ALGO_WAVEFRONT_AA: one camera sample's colour as raytrace() returns it
+// (raytrace.rs:271-275 with one camera sample: BLACK + c, divided by 1).
+__device__ __forceinline__ Col aa_sample(Col c) { return Col{(0.0 + c.r) / 1.0, (0.0 + c.g) / 1.0, (0.0 + c.b) / 1.0}; }
+
+// ... and main.rs:47-55's `res = res + raytrace(..)` for sample fp.aa_pass of chunk
+// pixel p: pass 0 starts from BLACK (0.0 + s_0, nothing read), pass a adds s_a to
+// the sum of samples 0 .. a-1.  A pixel has one writer per pass and the passes
+// of a chunk follow each other on its lane's stream: plain loads and stores.
+__device__ __forceinline__ void aa_add(const FrameParams& fp, uint32_t p, Col s) {
+    double* q = fp.aa_acc + 3 * static_cast<size_t>(p);
+    Col acc{0.0, 0.0, 0.0};
+    if (fp.aa_pass) acc = Col{q[0], q[1], q[2]};
+    q[0] = acc.r + s.r; q[1] = acc.g + s.g; q[2] = acc.b + s.b;
+}
+
 // The final colour of chain c (pixel p of the chunk): into ccol[c] for wf_compose
-// (chain order: coalesced), or straight into the frame.
+// (chain order: coalesced), or straight into the frame.  kAa (res: the sample's
+// colour): into term[c] (the chain's terminal, folded by now) for wf_aa_compose,
+// or added to pixel p's running sum.
+template <bool kAa = false>
 __device__ __forceinline__ void emit_chain(const FrameParams& fp, const WfBufs& b, uint32_t c, uint32_t p, Col res,
                                            const double* srgb) {
-    if (b.compose) {
+    if constexpr (kAa) {
+        if (b.compose) { stn(&b.term(0)[c], res.r); stn(&b.term(1)[c], res.g); stn(&b.term(2)[c], res.b); }
+        else aa_add(fp, p, res);
+    } else if (b.compose) {
         const uint32_t q = static_cast<uint32_t>(to_srgb(res.b, srgb)) | (static_cast<uint32_t>(to_srgb(res.g, srgb)) << 8) |
                            (static_cast<uint32_t>(to_srgb(res.r, srgb)) << 16);
         const U32x4 v = {__float_as_uint(static_cast<float>(res.r)), __float_as_uint(static_cast<float>(res.g)),
@@ -596,7 +617,8 @@ __host__ __device__ inline size_t queue_lds_bytes(uint32_t G) { return (G + 1 + 
 // pixel cpix[c]); its records, reflection rays, levels and terminal carry c
 // (`p` is the pixel for kCam, the chain otherwise), so the levels and
 // terminals of a generation are written in about the order of its records.
-template <bool kCam, bool kFresnel>
+// kAa (kCam only): a camera ray that ends adds its sample's colour to the pixel's running sum.
+template <bool kCam, bool kFresnel, bool kAa = false>
 __device__ __forceinline__ void finish_nearest(const DevScene& sc, const FrameParams& fp, const WfBufs& b,
                                                const DevSphere* sph, int k, bool live, const Ray& r, double sig,
                                                uint32_t p, const Hit& h, uint32_t* counts, size_t obase, size_t rbase) {
@@ -611,6 +633,7 @@ __device__ __forceinline__ void finish_nearest(const DevScene& sc, const FramePa
         if (h.obj == INT32_MAX) {                                           // raytrace.rs:265, 228-232
             if constexpr (kCam) {                                           // no levels: final now
                 if (b.compose) stn(&b.pmap()[p], kPixBackground);
+                else if constexpr (kAa) aa_add(fp, p, Col{fp.aa_bg[0], fp.aa_bg[1], fp.aa_bg[2]});
                 else write_background_pixel(fp, b, p);
             } else {
                 ends = true;
@@ -644,6 +667,7 @@ __device__ __forceinline__ void finish_nearest(const DevScene& sc, const FramePa
     if (ends) {
         if constexpr (kCam) {                              // no levels: the final pixel now
             if (b.compose) stn(&b.pmap()[p], kPixAmbient | static_cast<uint32_t>(end_obj));
+            else if constexpr (kAa) aa_add(fp, p, aa_sample(end_colour(sc, end_obj)));
             else write_pixel(fp, p % fp.tile_w, fp.row0 + p / fp.tile_w, average_samples(end_colour(sc, end_obj), fp.spp));
         } else {
             set_terminal(b, p, end_colour(sc, end_obj), k);
@@ -688,7 +712,7 @@ __device__ __forceinline__ void finish_nearest(const DevScene& sc, const FramePa
 // its reflection ray (raytrace.rs:58-64) to Q_{k+1} right here: the next
 // generation depends only on the hit, never on the shadow rays or the Phong
 // sum, so those run on the other stream, off the critical path.
-template <int kSrc, bool kCam, bool kCount, bool kFresnel>
+template <int kSrc, bool kCam, bool kCount, bool kFresnel, bool kAa = false>
 __global__ __launch_bounds__(kWfThreads, Src<kSrc>::waves) void wf_nearest(DevScene sc, FrameParams fp, WfBufs b, int k) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
 #ifndef RT_NEAR_PRIO
@@ -734,7 +758,7 @@ __global__ __launch_bounds__(kWfThreads, Src<kSrc>::waves) void wf_nearest(DevSc
             if constexpr (kCam) {
                 uint32_t lx, ly;
                 if (slot_pixel(b, fp, j, lx, ly)) {
-                    r = camera_ray(sc, fp, lx, fp.row0 + ly);
+                    r = camera_ray(sc, fp, lx, fp.row0 + ly, fp.aa_pass);
                     sig = 1.0;                              // raytrace.rs:273 via main.rs:54
                     p = ly * fp.tile_w + lx;
                     live = true;
@@ -750,7 +774,7 @@ __global__ __launch_bounds__(kWfThreads, Src<kSrc>::waves) void wf_nearest(DevSc
         RT_STAMP_AT(st1);
         if (live) h = nearest_any<kSrc, kCount>(sc, v, r, &w);
         RT_STAMP_AT(st2);
-        finish_nearest<kCam, kFresnel>(sc, fp, b, v.sph, k, live, r, sig, p, h, ql.count, obase, rbase);
+        finish_nearest<kCam, kFresnel, kAa>(sc, fp, b, v.sph, k, live, r, sig, p, h, ql.count, obase, rbase);
         RT_STAMP_AT(st3);
 #if RT_STAMP
         acc[1] += st1 - st0; acc[2] += st2 - st1; acc[3] += st3 - st2; acc[4] += 1;
@@ -1069,7 +1093,7 @@ __device__ __forceinline__ Col fold_pixel(const DevScene& sc, const WfBufs& b, u
 // record loads and level stores stay coalesced.  gridDim.x workgroups, all
 // resident; workgroup w publishes its counts in region w and zeros in the
 // other regions r = w (mod gridDim.x) of every generation >= T.
-template <bool kFresnel, bool kCount>
+template <bool kFresnel, bool kCount, bool kAa = false>
 __global__ __launch_bounds__(kWfThreads, 4) void wf_tail(DevScene sc, FrameParams fp, WfBufs b, int T, int W) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     __shared__ uint32_t s_cnt[2][kMaxGenerations];
@@ -1094,8 +1118,9 @@ __global__ __launch_bounds__(kWfThreads, 4) void wf_tail(DevScene sc, FrameParam
         const ShadeIn in = shade_load(b, at, false);
         int nlev = 0;
         const Col term = tail_chain<kFresnel, kCount>(sc, fp, b, v, T - 1, in, nlev, s_cnt, wn, wsh);
-        const Col res = average_samples(fold_levels<kFresnel>(sc, b, in.c, nlev, term), fp.spp);
-        emit_chain(fp, b, in.c, b.compose ? 0u : b.cpix()[in.c], res, s_srgb);
+        const Col folded = fold_levels<kFresnel>(sc, b, in.c, nlev, term);
+        const Col res = kAa ? aa_sample(folded) : average_samples(folded, fp.spp);
+        emit_chain<kAa>(fp, b, in.c, b.compose ? 0u : b.cpix()[in.c], res, s_srgb);
     }
     __syncthreads();
     for (uint32_t rg = blockIdx.x; rg < b.G; rg += gridDim.x) {
@@ -1126,7 +1151,7 @@ __global__ __launch_bounds__(kWfThreads, 4) void wf_tail(DevScene sc, FrameParam
 // RT_FOLD_THREADS-thread workgroups (256: at the fold's ~96 VGPRs five of them,
 // 20 waves, fit a CU where one 1024-thread workgroup leaves 4 wave slots idle),
 // dealt block-major over (kWfThreads / RT_FOLD_THREADS) x G workgroups.
-template <bool kFresnel>
+template <bool kFresnel, bool kAa = false>
 __global__ __launch_bounds__(RT_FOLD_THREADS, RT_FOLD_WAVES) void wf_fold(DevScene sc, FrameParams fp, WfBufs b, uint32_t lo,
                                                                           uint32_t hi) {
     constexpr int kT = RT_FOLD_THREADS;
@@ -1159,8 +1184,9 @@ __global__ __launch_bounds__(RT_FOLD_THREADS, RT_FOLD_WAVES) void wf_fold(DevSce
     for (; static_cast<uint64_t>(rc) * 64u < n; rc += W) {
         const Head nxt = head(static_cast<uint64_t>(rc + W) * 64u + lane);
         if (cur.nlev >= lo && cur.nlev <= hi) {             // (kNlevRunning: not ended yet, or no chain)
-            const Col res = average_samples(fold_levels<kFresnel>(sc, b, cur.c, static_cast<int>(cur.nlev), cur.term), fp.spp);
-            emit_chain(fp, b, cur.c, cur.p, res, s_srgb);
+            const Col folded = fold_levels<kFresnel>(sc, b, cur.c, static_cast<int>(cur.nlev), cur.term);
+            const Col res = kAa ? aa_sample(folded) : average_samples(folded, fp.spp);
+            emit_chain<kAa>(fp, b, cur.c, cur.p, res, s_srgb);
         }
         cur = nxt;
     }
@@ -1171,9 +1197,64 @@ hipError_t launch_fold(const DevScene& sc, const FrameParams& fp, const WfBufs& 
     hipError_t e;
     if (m && (e = m->begin(s)) != hipSuccess) return e;
     const dim3 grid(b.G * (kWfThreads / RT_FOLD_THREADS)), block(RT_FOLD_THREADS);
-    if (sc.has_fresnel) hipLaunchKernelGGL((wf_fold<true>), grid, block, 0, s, sc, fp, b, lo, hi);
+    if (fp.aa_acc) {                           // RT_ALGO_WAVEFRONT_AA: the sample's colour to the running sums
+        if (sc.has_fresnel) hipLaunchKernelGGL((wf_fold<true, true>), grid, block, 0, s, sc, fp, b, lo, hi);
+        else hipLaunchKernelGGL((wf_fold<false, true>), grid, block, 0, s, sc, fp, b, lo, hi);
+    } else if (sc.has_fresnel) hipLaunchKernelGGL((wf_fold<true>), grid, block, 0, s, sc, fp, b, lo, hi);
     else hipLaunchKernelGGL((wf_fold<false>), grid, block, 0, s, sc, fp, b, lo, hi);
     return m ? m->mark(s, kKfFold) : hipGetLastError();
+}
+
+// One wave's 64-pixel segment of a frame row (pixels [x0, x0 + nv) of chunk row lrow; lane's
+// pixel: f32 r, g, bl and sRGB bytes q = b | g << 8 | r << 16): the f32 RGB as consecutive dwords
+// and the BGR as consecutive dwords (dw) or bytes, staged through the wave's LDS slices so that
+// every store instruction covers consecutive addresses; the row's zero padding after its last
+// segment.  Wave-uniform arguments but r, g, bl, q.
+__device__ __forceinline__ void store_row_segment(const FrameParams& fp, float* s_rgb, uint32_t* s_bgr, bool dw, uint32_t lrow,
+                                                  uint32_t x0, uint32_t nv, float r, float g, float bl, uint32_t q) {
+    const uint32_t lane = threadIdx.x & 63u, x = x0 + lane;
+    const uint32_t orow = fp.row0 + lrow;
+    if (fp.out_rgb) {
+        s_rgb[3 * lane] = r; s_rgb[3 * lane + 1] = g; s_rgb[3 * lane + 2] = bl;
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        float* dst = fp.out_rgb + (static_cast<size_t>(orow) * fp.tile_w + x0) * 3;
+#pragma unroll
+        for (uint32_t j = 0; j < 3; ++j) {
+            const uint32_t i = lane + 64u * j;
+            if (i < 3 * nv) dst[i] = s_rgb[i];
+        }
+    }
+    if (fp.out_bgr) {
+        uint8_t* row = fp.out_bgr + static_cast<size_t>(orow) * fp.bgr_pitch;
+        if (dw) {
+            uint8_t* sb = reinterpret_cast<uint8_t*>(s_bgr);
+            sb[3 * lane] = static_cast<uint8_t>(q); sb[3 * lane + 1] = static_cast<uint8_t>(q >> 8);
+            sb[3 * lane + 2] = static_cast<uint8_t>(q >> 16);
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            // dwords [0, ceil(3 nv / 4)) of the segment; bytes past 3 nv are row padding (zero)
+            const uint32_t nd = (3 * nv + 3) / 4;
+            if (lane < nd) {
+                uint32_t v = s_bgr[lane];
+                const uint32_t valid = 3 * nv - 4 * lane;                // bytes of this dword that are pixels
+                if (valid < 4) v &= (1u << (8 * valid)) - 1u;
+                reinterpret_cast<uint32_t*>(row + 3 * x0)[lane] = v;
+            }
+            __builtin_amdgcn_wave_barrier();
+        } else if (lane < nv) {
+            row[3 * x] = static_cast<uint8_t>(q); row[3 * x + 1] = static_cast<uint8_t>(q >> 8);
+            row[3 * x + 2] = static_cast<uint8_t>(q >> 16);
+        }
+        if (x0 + nv == fp.tile_w)                                  // BMP row padding is zero (main.rs:42)
+            for (uint32_t k = (dw ? (3 * fp.tile_w + 3) & ~3u : 3 * fp.tile_w) + lane; k < fp.pad_end; k += 64)
+                row[k] = 0;
+    }
+    __builtin_amdgcn_wave_barrier();
+}
+// dword-aligned BGR rows whose last dword the render may write whole (pixels, then zero padding)
+__device__ __forceinline__ bool bgr_dwords(const FrameParams& fp) {
+    return ((fp.bgr_pitch | reinterpret_cast<uintptr_t>(fp.out_bgr)) & 3u) == 0 && ((3 * fp.tile_w + 3) & ~3u) <= fp.pad_end;
 }
 
 // The frame of the chunk, row by row (WfBufs::compose): each wave writes 64
@@ -1193,8 +1274,7 @@ __global__ __launch_bounds__(kWfThreads) void wf_compose(DevScene sc, FrameParam
     const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
     const uint32_t segs = (fp.tile_w + 63u) / 64u;                    // 64-pixel segments per row
     const uint64_t total = static_cast<uint64_t>(segs) * fp.rows;
-    // dword-aligned BGR rows whose last dword the render may write whole (pixels, then zero padding)
-    const bool dw = ((fp.bgr_pitch | reinterpret_cast<uintptr_t>(fp.out_bgr)) & 3u) == 0 && ((3 * fp.tile_w + 3) & ~3u) <= fp.pad_end;
+    const bool dw = bgr_dwords(fp);
     for (uint64_t sg = static_cast<uint64_t>(blockIdx.x) * kComposeWaves + wave; sg < total;
          sg += static_cast<uint64_t>(gridDim.x) * kComposeWaves) {     // wave-uniform
         const uint32_t lrow = static_cast<uint32_t>(sg / segs), x0 = static_cast<uint32_t>(sg % segs) * 64u;
@@ -1218,44 +1298,60 @@ __global__ __launch_bounds__(kWfThreads) void wf_compose(DevScene sc, FrameParam
                 q = cc[3];
             }
         }
-        const uint32_t orow = fp.row0 + lrow;
-        if (fp.out_rgb) {
-            s_rgb[wave][3 * lane] = r; s_rgb[wave][3 * lane + 1] = g; s_rgb[wave][3 * lane + 2] = bl;
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            float* dst = fp.out_rgb + (static_cast<size_t>(orow) * fp.tile_w + x0) * 3;
-#pragma unroll
-            for (uint32_t j = 0; j < 3; ++j) {
-                const uint32_t i = lane + 64u * j;
-                if (i < 3 * nv) dst[i] = s_rgb[wave][i];
-            }
+        store_row_segment(fp, s_rgb[wave], s_bgr[wave], dw, lrow, x0, nv, r, g, bl, q);
+    }
+}
+
+// RT_ALGO_WAVEFRONT_AA with the compose route: what wf_compose is to a frame, for one pass's
+// running sums.  Row by row, 64 consecutive pixels per wave: the pass's sample colour of each
+// pixel from the pixel map (the background's, an ambient end's, or the chain's, which the fold
+// left in term[chain]) is added to the pixel's running sum (aa_add: coalesced).
+__global__ __launch_bounds__(kWfThreads) void wf_aa_compose(DevScene sc, FrameParams fp, WfBufs b) {
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+    const uint32_t segs = (fp.tile_w + 63u) / 64u;
+    const uint64_t total = static_cast<uint64_t>(segs) * fp.rows;
+    for (uint64_t sg = static_cast<uint64_t>(blockIdx.x) * kComposeWaves + wave; sg < total;
+         sg += static_cast<uint64_t>(gridDim.x) * kComposeWaves) {
+        const uint32_t lrow = static_cast<uint32_t>(sg / segs), x = static_cast<uint32_t>(sg % segs) * 64u + lane;
+        if (x >= fp.tile_w) continue;
+        const uint32_t p = lrow * fp.tile_w + x;
+        const uint32_t code = ldn(&b.pmap()[p]);
+        Col s;
+        if (code == kPixBackground) s = Col{fp.aa_bg[0], fp.aa_bg[1], fp.aa_bg[2]};
+        else if (code & kPixAmbient) s = aa_sample(end_colour(sc, static_cast<int32_t>(code & ~kPixAmbient)));
+        else s = Col{ldn(&b.term(0)[code]), ldn(&b.term(1)[code]), ldn(&b.term(2)[code])};
+        aa_add(fp, p, s);
+    }
+}
+
+// RT_ALGO_WAVEFRONT_AA, after the last pass of a chunk: the pixel is the running sum of its
+// fp.aa_spp samples divided by their number (main.rs:56), rounded once to f32 and quantised
+// from the f64 value; written row by row as wf_compose writes a frame.
+__global__ __launch_bounds__(kWfThreads) void wf_resolve(FrameParams fp) {
+    __shared__ float s_rgb[kComposeWaves][192];
+    __shared__ uint32_t s_bgr[kComposeWaves][48];
+    __shared__ double s_srgb[255];
+    for (int i = threadIdx.x; i < 255; i += kWfThreads) s_srgb[i] = c_srgb_avg[i];
+    __syncthreads();
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+    const uint32_t segs = (fp.tile_w + 63u) / 64u;
+    const uint64_t total = static_cast<uint64_t>(segs) * fp.rows;
+    const bool dw = bgr_dwords(fp);
+    const double aa = static_cast<double>(fp.aa_spp);
+    for (uint64_t sg = static_cast<uint64_t>(blockIdx.x) * kComposeWaves + wave; sg < total;
+         sg += static_cast<uint64_t>(gridDim.x) * kComposeWaves) {     // wave-uniform
+        const uint32_t lrow = static_cast<uint32_t>(sg / segs), x0 = static_cast<uint32_t>(sg % segs) * 64u;
+        const uint32_t nv = min(64u, fp.tile_w - x0);
+        float r = 0.0f, g = 0.0f, bl = 0.0f;
+        uint32_t q = 0;
+        if (lane < nv) {
+            const double* a = fp.aa_acc + 3 * (static_cast<size_t>(lrow) * fp.tile_w + x0 + lane);
+            const Col res{ldn(&a[0]) / aa, ldn(&a[1]) / aa, ldn(&a[2]) / aa};
+            r = static_cast<float>(res.r); g = static_cast<float>(res.g); bl = static_cast<float>(res.b);
+            q = static_cast<uint32_t>(to_srgb(res.b, s_srgb)) | (static_cast<uint32_t>(to_srgb(res.g, s_srgb)) << 8) |
+                (static_cast<uint32_t>(to_srgb(res.r, s_srgb)) << 16);
         }
-        if (fp.out_bgr) {
-            uint8_t* row = fp.out_bgr + static_cast<size_t>(orow) * fp.bgr_pitch;
-            if (dw) {
-                uint8_t* sb = reinterpret_cast<uint8_t*>(s_bgr[wave]);
-                sb[3 * lane] = static_cast<uint8_t>(q); sb[3 * lane + 1] = static_cast<uint8_t>(q >> 8);
-                sb[3 * lane + 2] = static_cast<uint8_t>(q >> 16);
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                // dwords [0, ceil(3 nv / 4)) of the segment; bytes past 3 nv are row padding (zero)
-                const uint32_t nd = (3 * nv + 3) / 4;
-                if (lane < nd) {
-                    uint32_t v = s_bgr[wave][lane];
-                    const uint32_t valid = 3 * nv - 4 * lane;                // bytes of this dword that are pixels
-                    if (valid < 4) v &= (1u << (8 * valid)) - 1u;
-                    reinterpret_cast<uint32_t*>(row + 3 * x0)[lane] = v;
-                }
-                __builtin_amdgcn_wave_barrier();
-            } else if (lane < nv) {
-                row[3 * x] = static_cast<uint8_t>(q); row[3 * x + 1] = static_cast<uint8_t>(q >> 8);
-                row[3 * x + 2] = static_cast<uint8_t>(q >> 16);
-            }
-            if (x0 + nv == fp.tile_w)                                  // BMP row padding is zero (main.rs:42)
-                for (uint32_t k = (dw ? (3 * fp.tile_w + 3) & ~3u : 3 * fp.tile_w) + lane; k < fp.pad_end; k += 64)
-                    row[k] = 0;
-        }
-        __builtin_amdgcn_wave_barrier();
+        store_row_segment(fp, s_rgb[wave], s_bgr[wave], dw, lrow, x0, nv, r, g, bl, q);
     }
 }
 
@@ -1370,6 +1466,8 @@ __global__ __launch_bounds__(kWfThreads) void wf_tally(FrameParams fp, WfBufs b,
         atomicAdd(&b.totals[0], nearest * fp.spp);
         atomicAdd(&b.totals[1], shadow * fp.spp);
     }
+    // (RT_ALGO_WAVEFRONT_AA: the queue sizes of the last pass of the last chunk only)
+    if (fp.aa_acc && !(fp.aa_flags & kAaTallyGens)) return;
     for (int g = threadIdx.x; g < generations; g += kWfThreads) {
         atomicAdd(&b.gen_totals[kCntQ + g], s_sum[g]);
         atomicAdd(&b.gen_totals[kCntS + g], s_sum[kMaxGenerations + g]);
@@ -1456,23 +1554,29 @@ hipError_t launch_generation(const DevScene& sc, const FrameParams& fp, const Wf
             return e;
         if (ws.ma && (e = ws.ma->begin(ws.a)) != hipSuccess) return e;
         const size_t lds_t = staged_bytes<kSrcBvhL8C>(sc) + queue_lds_bytes(b.G);
-        if (sc.has_fresnel) hipLaunchKernelGGL((wf_tail<true, kCount>), dim3(ws.tail_wgs), block, lds_t, ws.a, sc, fp, b, k, ws.tail_width);
-        else hipLaunchKernelGGL((wf_tail<false, kCount>), dim3(ws.tail_wgs), block, lds_t, ws.a, sc, fp, b, k, ws.tail_width);
+#define RT_TAIL(FR, AA) hipLaunchKernelGGL((wf_tail<FR, kCount, AA>), dim3(ws.tail_wgs), block, lds_t, ws.a, sc, fp, b, k, ws.tail_width)
+        if (fp.aa_acc) { if (sc.has_fresnel) RT_TAIL(true, true); else RT_TAIL(false, true); }
+        else if (sc.has_fresnel) RT_TAIL(true, false);
+        else RT_TAIL(false, false);
+#undef RT_TAIL
         return ws.ma ? ws.ma->mark(ws.a, kKfTail) : hipGetLastError();
     }
     e = ws.ma ? ws.ma->begin(ws.a) : hipSuccess;
     if (e != hipSuccess) return e;
-#define RT_NEAR(S, CAM, FR) hipLaunchKernelGGL((wf_nearest<S, CAM, kCount, FR>), grid, block, \
-                                               staged_bytes<S>(sc) + queue_lds_bytes(b.G), ws.a, sc, fp, b, k)
-    if (k == 0 && ws.cam == 3) {                 // the camera's view grid, spheres in LDS
-        if (sc.has_fresnel) RT_NEAR(kSrcCamGridL, true, true); else RT_NEAR(kSrcCamGridL, true, false);
-    } else if (k == 0 && ws.cam == 4) {          // ... spheres through L2
-        if (sc.has_fresnel) RT_NEAR(kSrcCamGridG, true, true); else RT_NEAR(kSrcCamGridG, true, false);
-    } else if (k == 0) {
-        if (sc.has_fresnel) RT_NEAR(kSrcN, true, true); else RT_NEAR(kSrcN, true, false);
-    } else {
-        if (sc.has_fresnel) RT_NEAR(kSrcN, false, true); else RT_NEAR(kSrcN, false, false);
-    }
+#define RT_NEAR(S, CAM, FR, AA) hipLaunchKernelGGL((wf_nearest<S, CAM, kCount, FR, AA>), grid, block, \
+                                                   staged_bytes<S>(sc) + queue_lds_bytes(b.G), ws.a, sc, fp, b, k)
+    // the camera pass of RT_ALGO_WAVEFRONT_AA (fp.aa_acc): its own instantiations, the others are untouched
+#define RT_CAM(S) do {                                                                                          \
+        if (fp.aa_acc) { if (sc.has_fresnel) RT_NEAR(S, true, true, true); else RT_NEAR(S, true, false, true); }  \
+        else if (sc.has_fresnel) RT_NEAR(S, true, true, false);                                                  \
+        else RT_NEAR(S, true, false, false);                                                                     \
+    } while (0)
+    if (k == 0 && ws.cam == 3) RT_CAM(kSrcCamGridL);            // the camera's view grid, spheres in LDS
+    else if (k == 0 && ws.cam == 4) RT_CAM(kSrcCamGridG);       // ... spheres through L2
+    else if (k == 0) RT_CAM(kSrcN);
+    else if (sc.has_fresnel) RT_NEAR(kSrcN, false, true, false);
+    else RT_NEAR(kSrcN, false, false, false);
+#undef RT_CAM
 #undef RT_NEAR
     e = ws.ma ? ws.ma->mark(ws.a, k == 0 ? kKfCamera : kKfNearest) : hipSuccess;
     if (e != hipSuccess) return e;
@@ -1547,11 +1651,24 @@ hipError_t launch_wavefront(const DevScene& sc, const FrameParams& fp, const WfB
     // the chains not folded yet (all of them without the fused tail, which folded every chain:
     // its own as it ended them, the others on a B stream)
     if (ws.tail_fuse == 0 && (e = launch_fold(sc, fp, b, ws.a, ws.ma, 0u, kNlevRunning - 1u)) != hipSuccess) return e;
-    if (b.compose) {                         // the frame, row by row, once every chain has its colour
+    const uint64_t segs = static_cast<uint64_t>((fp.tile_w + 63u) / 64u) * fp.rows;
+    const dim3 row_grid(std::max(1u, static_cast<uint32_t>(std::min<uint64_t>(4u * b.G, (segs + kComposeWaves - 1) / kComposeWaves))));
+    if (fp.aa_acc) {
+        // RT_ALGO_WAVEFRONT_AA: the pass has added its sample to the running sums (compose: does so
+        // now, row by row); after the chunk's last pass wf_resolve writes the chunk's rows
+        if (b.compose) {
+            if (ws.ma && (e = ws.ma->begin(ws.a)) != hipSuccess) return e;
+            hipLaunchKernelGGL(wf_aa_compose, row_grid, dim3(kWfThreads), 0, ws.a, sc, fp, b);
+            if (ws.ma && (e = ws.ma->mark(ws.a, kKfCompose)) != hipSuccess) return e;
+        }
+        if (fp.aa_pass + 1 == fp.aa_spp) {
+            if (ws.ma && (e = ws.ma->begin(ws.a)) != hipSuccess) return e;
+            hipLaunchKernelGGL(wf_resolve, row_grid, dim3(kWfThreads), 0, ws.a, fp);
+            if (ws.ma && (e = ws.ma->mark(ws.a, kKfCompose)) != hipSuccess) return e;
+        }
+    } else if (b.compose) {                  // the frame, row by row, once every chain has its colour
         if (ws.ma && (e = ws.ma->begin(ws.a)) != hipSuccess) return e;
-        const uint64_t segs = static_cast<uint64_t>((fp.tile_w + 63u) / 64u) * fp.rows;
-        const uint32_t wgs = static_cast<uint32_t>(std::min<uint64_t>(4u * b.G, (segs + kComposeWaves - 1) / kComposeWaves));
-        hipLaunchKernelGGL(wf_compose, dim3(std::max(1u, wgs)), dim3(kWfThreads), 0, ws.a, sc, fp, b);
+        hipLaunchKernelGGL(wf_compose, row_grid, dim3(kWfThreads), 0, ws.a, sc, fp, b);
         if (ws.ma && (e = ws.ma->mark(ws.a, kKfCompose)) != hipSuccess) return e;
     }
     if (ws.sp_s) {                           // the chain pixels' segments, packed in row order

@@ -113,7 +113,11 @@ namespace rtamd {
     /* 1: the b streams join the chain's stream on the device (a one-wave                                            \
        kernel polling a flag the b stream's last kernel is followed by),                                             \
        0: through events (a barrier packet on the chain's queue) */                                                  \
-    X(DevJoin, "dev_join", 1, 0, 1)
+    X(DevJoin, "dev_join", 1, 0, 1)                                                                                  \
+    /* 1: RT_ALGO_AUTO renders a chain-class scene (<= 32 lights) with random                                        \
+       jitter and spp > 1 as RT_ALGO_WAVEFRONT_AA (one chain pass per AA                                             \
+       sample) instead of on the path kernel */                                                \
+    X(AaWavefront, "aa_wavefront", 0, 0, 1)
 
 enum TuneKey : int {
 #define RT_TUNE_ENUM(id, name, dflt, lo, hi) kTune##id,

@@ -20,7 +20,7 @@ PKG_DIR = os.path.dirname(_HERE)
 LIB_PATH = os.environ.get("RT_LIBRTAMD") or os.path.join(PKG_DIR, "librtamd.so")
 HEADER_PATH = os.path.join(os.path.dirname(PKG_DIR), "include", "raytrace_amd.h")
 
-RT_ABI_VERSION = 5               # include/raytrace_amd.h
+RT_ABI_VERSION = 6               # include/raytrace_amd.h
 RT_OK = 0
 RT_E_INVALID, RT_E_NODEVICE, RT_E_HIP, RT_E_NOMEM = -1, -2, -3, -4
 RT_E_UNSUPPORTED, RT_E_PARSE, RT_E_NOSCENE, RT_E_IO = -5, -6, -7, -8
@@ -33,6 +33,7 @@ RT_OUT_RGB_F32, RT_OUT_BGR_U8, RT_COUNT_WORK, RT_TIME_KERNELS, RT_OUT_FRAME_ROWS
 KERNEL_FAMILIES = ("nearest", "occlusion", "shade", "fold", "tally", "camera", "compose", "tail")   # rt_kernel_family
 RT_ALGO_AUTO, RT_ALGO_BRUTE_LDS, RT_ALGO_BRUTE_GLOBAL, RT_ALGO_WAVEFRONT, RT_ALGO_WAVEFRONT_BRUTE = 0, 1, 2, 3, 4
 RT_ALGO_PATH = 5
+RT_ALGO_WAVEFRONT_AA = 6        # one wavefront pass per jittered AA sample
 RT_JITTER_CENTER, RT_JITTER_RANDOM = 0, 1
 RT_MAX_DEPTH_LIMIT = 30
 
