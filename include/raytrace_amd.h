@@ -210,7 +210,9 @@ int rt_ctx_create(int device, rt_ctx** out);
 void rt_ctx_destroy(rt_ctx* ctx);
 const char* rt_last_error(const rt_ctx* ctx);
 /* Copies the scene to HBM in the device layout.  Classes the device path does
- * not implement -> RT_E_UNSUPPORTED. */
+ * not implement -> RT_E_UNSUPPORTED.  A SkyboxBackground's texels go with every
+ * scene that has one and do not choose the schedule: a skybox scene of chain classes (Phong /
+ * Fresnel, point / directional lights, the simple camera) renders on every rt_algo. */
 int rt_scene_upload(rt_ctx* ctx, const rt_scene* scene);
 
 enum rt_jitter {
@@ -236,16 +238,19 @@ enum rt_algo {
     RT_ALGO_BRUTE_GLOBAL = 2,   /* megakernel, sphere list read through the caches */
     RT_ALGO_WAVEFRONT = 3,      /* per-depth launches over compacted ray queues, sphere BVH (default) */
     RT_ALGO_WAVEFRONT_BRUTE = 4, /* the same schedule, every sphere tested (linear scan like scene.rs:248) */
+                                /* (1-4 and 6, the chain algorithms: solid or skybox background; a ray that misses
+                                   takes the skybox's colour in its direction, raytrace.rs:234-256) */
     RT_ALGO_PATH = 5,           /* per-pixel recursion over an HBM stack: every material / light / camera class
                                    (IndirectPhong, Transparent, AreaLight, DepthOfField, random jitter); AUTO picks
-                                   it whenever the scene or the jitter mode needs it */
+                                   it whenever the scene or the jitter mode needs it (a skybox alone does not) */
     RT_ALGO_WAVEFRONT_AA = 6    /* RT_ALGO_WAVEFRONT's schedule run once per AA sample (main.rs:47-56): every sample
                                    of a pixel gets its own jitter (rt_jitter, any spp >= 1) and its own ray tree;
                                    the samples are summed in f64 in sample order and divided by spp, bit for bit
                                    what RT_ALGO_PATH renders.  With RT_JITTER_CENTER or spp 1 it is
                                    RT_ALGO_WAVEFRONT's render.  A scene that needs RT_ALGO_PATH (IndirectPhong,
                                    Transparent, AreaLight, DepthOfField) or has more than 32 lights ->
-                                   RT_E_UNSUPPORTED.  AUTO picks it only under tuning aa_wavefront. */
+                                   RT_E_UNSUPPORTED.  AUTO picks it only under tuning aa_wavefront.  Skybox: a
+                                   sample whose camera ray misses adds the skybox's colour along that sample's ray. */
 };
 
 typedef struct {
@@ -346,7 +351,9 @@ enum rt_kernel_family {
     RT_KF_TALLY = 4,        /* wf_tally */
     RT_KF_CAMERA = 5,       /* wf_nearest, generation 0 (camera rays) */
     RT_KF_COMPOSE = 6,      /* wf_compose: the row-ordered frame pass (tuning compose); RT_ALGO_WAVEFRONT_AA:
-                               wf_resolve after a chunk's last pass (and wf_aa_compose per pass, tuning compose) */
+                               wf_resolve after a chunk's last pass (and wf_aa_compose per pass, tuning compose);
+                               skybox scenes: wf_sky_pixels after the camera pass (compose 0) and wf_sky_term
+                               before each fold */
     RT_KF_TAIL = 7,         /* wf_tail: the fused generations >= tail_fuse */
     RT_KF_COUNT = 8
 };

@@ -152,7 +152,8 @@ struct DevScene {
     int32_t pfx2;                   // prefix sources: nodes of the binary tree staged in LDS (set per render)
     int32_t needs_path;             // a class only the path kernel implements (IndirectPhong, Transparent,
                                     // AreaLight, DepthOfFieldCamera)
-    int32_t skybox;                 // SkyboxBackground (raytrace.rs:234-256; path kernel only)
+    int32_t skybox;                 // SkyboxBackground (raytrace.rs:234-256): every schedule samples it for a ray
+                                    // that misses (trace_common.hpp background(); chain schedules: DESIGN.md §3.13)
     const uint8_t* tex;             // skybox texels
     const double* srgb_values;      // color.rs SRGB_VALUES (Color::from_srgb, color.rs:611-613)
     DevTexFace faces[6];            // px, nx, py, ny, pz, nz
@@ -185,8 +186,9 @@ struct FrameParams {
     float* out_rgb;                 // tile_h * tile_w * 3, may be null
     uint8_t* out_bgr;               // tile_h * bgr_pitch, may be null
     unsigned long long* counters;   // [kCounterShards] rays, then [kCounterShards] shadow rays
-    float bg_rgb[3];                // output of a pixel whose camera ray misses: the background
-    uint8_t bg_bgr[3];              //   averaged over spp (main.rs:56), f32 and sRGB B,G,R (host-computed)
+    float bg_rgb[3];                // output of a pixel whose camera ray misses: the solid background
+    uint8_t bg_bgr[3];              //   averaged over spp (main.rs:56), f32 and sRGB B,G,R (host-computed; a skybox
+                                    //   scene's kernels do not read them, nor aa_bg)
     int32_t jitter;                 // rt_jitter: 0 centre, 1 keyed random draws (path kernel)
     uint64_t seed;                  // keyed RNG seed (path kernel)
     const double* srgb;             // the 255 sRGB thresholds in HBM (path kernel stages them in LDS)
@@ -273,7 +275,8 @@ struct PathStack {
 //   pmap     (compose) per chunk pixel [cap]: its chain, or kPixBackground /
 //            kPixAmbient | object for a camera ray that ended without a chain;
 //            With mark (sparse host copies) its first cap bytes are cmark
-//            instead: 1 for a pixel that starts a chain, else 0;
+//            instead: 1 for a pixel that starts a chain, else 0; without compose on a
+//            skybox scene its next cap bytes are csky: 1 for a camera ray that missed;
 //   ccol     (compose) per chain [capa]: final colour f32 r,g,b and the sRGB
 //            bytes b | g << 8 | r << 16 (16 B), written by the fold in chain
 //            order and read by wf_compose, which writes the frame row by row.
@@ -325,10 +328,15 @@ struct WfBufs {
     // (mark) chunk pixel -> 1 if a chain starts there, 0 if the camera pass wrote its final colour
     // (the pmap section's bytes: compose and mark are never on together)
     RT_HD uint8_t* cmark() const { return mem + o_pmap; }
+    // (skybox scene, compose 0) chunk pixel -> 1 if its camera ray missed every object: wf_sky_pixels
+    // writes that pixel.  The pmap section's bytes [cap, 2 cap): beside cmark, never with pmap.
+    RT_HD uint8_t* csky() const { return mem + o_pmap + cap; }
     RT_HD uint32_t* rq() const { return reinterpret_cast<uint32_t*>(mem + o_rq); }
     RT_HD uint32_t* rs() const { return reinterpret_cast<uint32_t*>(mem + o_rs); }
 };
 constexpr uint32_t kNlevRunning = 0xFFu;   // WfBufs::nlev of a chain that has not ended yet
+constexpr uint32_t kNlevSky = 0x80u;       // ... | levels (skybox scene): the chain's last ray missed and term holds its
+                                           //   direction, not a colour, until wf_sky_term samples the skybox there
 constexpr uint32_t kPixBackground = 0xFFFFFFFFu;   // WfBufs::pmap: the camera ray missed every object
 constexpr uint32_t kPixAmbient = 0x80000000u;      // ... | object: it ended on that object's ambient colour
 

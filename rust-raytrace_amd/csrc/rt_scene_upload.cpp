@@ -207,9 +207,9 @@ int rt_qtree_nodes(const rt_scene* s, int leaf_max, void* nodes, float* boxes, i
 
 static int scene_upload(rt_ctx* c, const rt_scene* s) {
     HIP_TRY(c, hipSetDevice(c->device));
-    // Every class of the reference except SkyboxBackground (textures) has a
-    // device implementation: Phong / Fresnel chains on the wavefront path,
-    // the stochastic and branching classes on the path kernel (needs_path).
+    // Every class of the reference has a device implementation: Phong / Fresnel
+    // chains on the wavefront path, under a solid or a skybox background, the
+    // stochastic and branching classes on the path kernel (needs_path).
     if (s->background_kind != RT_BG_SOLID && s->background_kind != RT_BG_SKYBOX)
         return fail(c, RT_E_INVALID, "bad background kind");
     const bool skybox = s->background_kind == RT_BG_SKYBOX;
@@ -221,7 +221,7 @@ static int scene_upload(rt_ctx* c, const rt_scene* s) {
         return fail(c, RT_E_INVALID, "bad camera kind");
     if (s->camera.kind == RT_CAMERA_DOF && s->camera.samples == 0)
         return fail(c, RT_E_INVALID, "DepthOfFieldCamera with 0 samples");
-    bool needs_path = s->camera.kind == RT_CAMERA_DOF || skybox;
+    bool needs_path = s->camera.kind == RT_CAMERA_DOF;
     std::vector<DevSphere> spheres;
     std::vector<double> sx, sy, sz, srad;
     std::vector<int32_t> sphere_obj, plane_obj;

@@ -66,7 +66,9 @@ constexpr int kBlock = 256;                 // 4 waves
 
 // ---------------------------------------------------------------- megakernel
 
-template <class SpherePtr>
+// kSky (a skybox scene's instantiations): a ray that misses, at any depth, takes the skybox's colour in
+// its direction (raytrace.rs:234-256) instead of the solid background.
+template <bool kSky, class SpherePtr>
 __device__ Col trace_chain(const DevScene& sc, SpherePtr S, Ray ray, uint32_t max_depth, uint32_t& rays,
                            uint32_t& shadows) {
     double st_r[kMaxLevels], st_g[kMaxLevels], st_b[kMaxLevels], st_f[kMaxLevels];
@@ -78,7 +80,11 @@ __device__ Col trace_chain(const DevScene& sc, SpherePtr S, Ray ray, uint32_t ma
     for (;;) {
         const Hit h = nearest_brute(sc, S, ray);
         ++rays;
-        if (h.obj == INT32_MAX) { term = Col{sc.bg[0], sc.bg[1], sc.bg[2]}; break; }   // raytrace.rs:228-232
+        if (h.obj == INT32_MAX) {                                  // raytrace.rs:228-256
+            if constexpr (kSky) term = background(sc, ray);
+            else term = Col{sc.bg[0], sc.bg[1], sc.bg[2]};
+            break;
+        }
         const DevMaterial& m = sc.mats[h.obj];
         Col res{m.amb[0], m.amb[1], m.amb[2]};
         if (depth > max_depth) { term = res; break; }             // raytrace.rs:33
@@ -118,7 +124,7 @@ __device__ Col trace_chain(const DevScene& sc, SpherePtr S, Ray ray, uint32_t ma
     return acc;
 }
 
-template <bool kLds>
+template <bool kLds, bool kSky = false>
 __global__ __launch_bounds__(kBlock) void trace_frame_kernel(DevScene sc, FrameParams fp) {
     extern __shared__ __attribute__((aligned(16))) DevSphere lds_spheres[];
     if constexpr (kLds) {
@@ -133,8 +139,8 @@ __global__ __launch_bounds__(kBlock) void trace_frame_kernel(DevScene sc, FrameP
     if (lx < fp.tile_w && ly < fp.rows) {
         const Ray cam = camera_ray(sc, fp, lx, fp.row0 + ly, 0u);
         Col c;
-        if constexpr (kLds) c = trace_chain(sc, static_cast<const DevSphere*>(lds_spheres), cam, fp.max_depth, rays, shadows);
-        else c = trace_chain(sc, sc.spheres, cam, fp.max_depth, rays, shadows);
+        if constexpr (kLds) c = trace_chain<kSky>(sc, static_cast<const DevSphere*>(lds_spheres), cam, fp.max_depth, rays, shadows);
+        else c = trace_chain<kSky>(sc, sc.spheres, cam, fp.max_depth, rays, shadows);
         write_pixel(fp, lx, fp.row0 + ly, average_samples(c, fp.spp));
         rays *= fp.spp;          // identical centre-jitter samples: traced once, counted as the reference issues them
         shadows *= fp.spp;
@@ -591,6 +597,12 @@ __device__ __forceinline__ void set_terminal(const WfBufs& b, uint32_t c, Col co
     stn(&b.term(0)[c], col.r); stn(&b.term(1)[c], col.g); stn(&b.term(2)[c], col.b);
     b.nlev()[c] = static_cast<uint8_t>(k);
 }
+// ... on a skybox scene by a miss of ray r: the skybox is sampled later (wf_sky_term, before the
+// fold), so the traversal kernel carries no texel fetches; term holds the direction until then.
+__device__ __forceinline__ void set_sky_terminal(const WfBufs& b, uint32_t c, const Ray& r, int k) {
+    stn(&b.term(0)[c], r.dx); stn(&b.term(1)[c], r.dy); stn(&b.term(2)[c], r.dz);
+    b.nlev()[c] = static_cast<uint8_t>(kNlevSky | static_cast<uint32_t>(k));
+}
 
 // LDS of a queue kernel after its staged data.
 constexpr int kQueueCounters = 2;           // this workgroup's shade records and reflection rays
@@ -618,7 +630,11 @@ __host__ __device__ inline size_t queue_lds_bytes(uint32_t G) { return (G + 1 + 
 // (`p` is the pixel for kCam, the chain otherwise), so the levels and
 // terminals of a generation are written in about the order of its records.
 // kAa (kCam only): a camera ray that ends adds its sample's colour to the pixel's running sum.
-template <bool kCam, bool kFresnel, bool kAa = false>
+// kSky (a skybox scene's instantiations): a miss is not a constant.  A later
+// generation's leaves the ray's direction as the chain's terminal (set_sky_terminal); a camera
+// ray's is noted in pmap (compose, as ever) or csky, and wf_compose / wf_aa_compose / wf_sky_pixels
+// rebuild the ray and write the pixel or add its sample.
+template <bool kCam, bool kFresnel, bool kAa = false, bool kSky = false>
 __device__ __forceinline__ void finish_nearest(const DevScene& sc, const FrameParams& fp, const WfBufs& b,
                                                const DevSphere* sph, int k, bool live, const Ray& r, double sig,
                                                uint32_t p, const Hit& h, uint32_t* counts, size_t obase, size_t rbase) {
@@ -633,8 +649,11 @@ __device__ __forceinline__ void finish_nearest(const DevScene& sc, const FramePa
         if (h.obj == INT32_MAX) {                                           // raytrace.rs:265, 228-232
             if constexpr (kCam) {                                           // no levels: final now
                 if (b.compose) stn(&b.pmap()[p], kPixBackground);
+                else if constexpr (kSky) { /* csky below: wf_sky_pixels */ }
                 else if constexpr (kAa) aa_add(fp, p, Col{fp.aa_bg[0], fp.aa_bg[1], fp.aa_bg[2]});
                 else write_background_pixel(fp, b, p);
+            } else if constexpr (kSky) {
+                set_sky_terminal(b, p, r, k);
             } else {
                 ends = true;
             }
@@ -675,6 +694,9 @@ __device__ __forceinline__ void finish_nearest(const DevScene& sc, const FramePa
     }
     if constexpr (kCam) {
         if (b.mark && live) stn(&b.cmark()[p], static_cast<uint8_t>(shade ? 1 : 0));
+        if constexpr (kSky) {
+            if (!b.compose && live) stn(&b.csky()[p], static_cast<uint8_t>(h.obj == INT32_MAX ? 1 : 0));
+        }
     }
     const uint32_t slot = lds_append(&counts[0], shade);
     const uint32_t chain = kCam ? static_cast<uint32_t>(obase) + slot : p;   // (slot valid when shade)
@@ -712,7 +734,7 @@ __device__ __forceinline__ void finish_nearest(const DevScene& sc, const FramePa
 // its reflection ray (raytrace.rs:58-64) to Q_{k+1} right here: the next
 // generation depends only on the hit, never on the shadow rays or the Phong
 // sum, so those run on the other stream, off the critical path.
-template <int kSrc, bool kCam, bool kCount, bool kFresnel, bool kAa = false>
+template <int kSrc, bool kCam, bool kCount, bool kFresnel, bool kAa = false, bool kSky = false>
 __global__ __launch_bounds__(kWfThreads, Src<kSrc>::waves) void wf_nearest(DevScene sc, FrameParams fp, WfBufs b, int k) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
 #ifndef RT_NEAR_PRIO
@@ -774,7 +796,7 @@ __global__ __launch_bounds__(kWfThreads, Src<kSrc>::waves) void wf_nearest(DevSc
         RT_STAMP_AT(st1);
         if (live) h = nearest_any<kSrc, kCount>(sc, v, r, &w);
         RT_STAMP_AT(st2);
-        finish_nearest<kCam, kFresnel, kAa>(sc, fp, b, v.sph, k, live, r, sig, p, h, ql.count, obase, rbase);
+        finish_nearest<kCam, kFresnel, kAa, kSky>(sc, fp, b, v.sph, k, live, r, sig, p, h, ql.count, obase, rbase);
         RT_STAMP_AT(st3);
 #if RT_STAMP
         acc[1] += st1 - st0; acc[2] += st2 - st1; acc[3] += st3 - st2; acc[4] += 1;
@@ -996,7 +1018,7 @@ __device__ __forceinline__ uint32_t grid_shadow_mask(const DevScene& sc, const B
 // terminal colour and sets nlev (the generation it ended in) instead of writing
 // them: the caller folds the chain right away.  cnt[0][k] / cnt[1][k]: this
 // workgroup's shade records of generation k / rays queued for generation k.
-template <bool kFresnel, bool kCount>
+template <bool kFresnel, bool kCount, bool kSky>
 __device__ __forceinline__ Col tail_chain(const DevScene& sc, const FrameParams& fp, const WfBufs& b, const BvhView& v,
                                           int k, ShadeIn in, int& nlev, uint32_t (*cnt)[kMaxGenerations], Work& wn,
                                           Work& wsh) {
@@ -1012,7 +1034,10 @@ __device__ __forceinline__ Col tail_chain(const DevScene& sc, const FrameParams&
         if (k > k0 + 1) atomicAdd(&cnt[1][k], 1u);                         // (Q_T was counted by wf_nearest)
         const Hit h = nearest_any<kSrcBvhL8C, kCount>(sc, v, r, &wn);
         nlev = k;
-        if (h.obj == INT32_MAX) return end_colour(sc, INT32_MAX);          // raytrace.rs:265, 228-232
+        if (h.obj == INT32_MAX) {                                          // raytrace.rs:265, 228-256
+            if constexpr (kSky) return background(sc, r);                  // (folded at once: sampled here)
+            else return end_colour(sc, INT32_MAX);
+        }
         const DevMaterial& m = sc.mats[h.obj];
         if (static_cast<uint32_t>(k) > fp.max_depth) return end_colour(sc, h.obj);    // raytrace.rs:33
         in.ptx = r.ox + r.dx * h.t; in.pty = r.oy + r.dy * h.t; in.ptz = r.oz + r.dz * h.t;   // ray.cast(t)
@@ -1093,7 +1118,7 @@ __device__ __forceinline__ Col fold_pixel(const DevScene& sc, const WfBufs& b, u
 // record loads and level stores stay coalesced.  gridDim.x workgroups, all
 // resident; workgroup w publishes its counts in region w and zeros in the
 // other regions r = w (mod gridDim.x) of every generation >= T.
-template <bool kFresnel, bool kCount, bool kAa = false>
+template <bool kFresnel, bool kCount, bool kAa = false, bool kSky = false>
 __global__ __launch_bounds__(kWfThreads, 4) void wf_tail(DevScene sc, FrameParams fp, WfBufs b, int T, int W) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     __shared__ uint32_t s_cnt[2][kMaxGenerations];
@@ -1117,7 +1142,7 @@ __global__ __launch_bounds__(kWfThreads, 4) void wf_tail(DevScene sc, FrameParam
         const size_t at = rk + region_entry(ql.scan, b.G, b.R, static_cast<uint32_t>(j));
         const ShadeIn in = shade_load(b, at, false);
         int nlev = 0;
-        const Col term = tail_chain<kFresnel, kCount>(sc, fp, b, v, T - 1, in, nlev, s_cnt, wn, wsh);
+        const Col term = tail_chain<kFresnel, kCount, kSky>(sc, fp, b, v, T - 1, in, nlev, s_cnt, wn, wsh);
         const Col folded = fold_levels<kFresnel>(sc, b, in.c, nlev, term);
         const Col res = kAa ? aa_sample(folded) : average_samples(folded, fp.spp);
         emit_chain<kAa>(fp, b, in.c, b.compose ? 0u : b.cpix()[in.c], res, s_srgb);
@@ -1192,9 +1217,68 @@ __global__ __launch_bounds__(RT_FOLD_THREADS, RT_FOLD_WAVES) void wf_fold(DevSce
     }
 }
 
+// The two sky passes of a skybox scene (both timed under RT_KF_COMPOSE), so that
+// no traversal kernel and no fold fetches a texel.
+//
+// wf_sky_term, before a fold: every chain that ended on a miss (nlev carries kNlevSky, term the
+// missing ray's direction: set_sky_terminal) gets its terminal colour, the skybox in that direction
+// (Background::color reads nothing else of the ray), and its plain level count.  Chains dealt as
+// wf_fold deals them; a chain still running (kNlevRunning) or ended on a colour is left alone, so
+// the pass may run before the early fold of the fused tail and again before the last one.
+__global__ __launch_bounds__(RT_FOLD_THREADS) void wf_sky_term(DevScene sc, WfBufs b) {
+    constexpr int kT = RT_FOLD_THREADS;
+    __shared__ uint32_t s_scan[kMaxRegions + 1];
+    __shared__ uint32_t s_wave[kT / 64];
+    region_scan<kT>(b.rs(), b.G, s_scan, s_wave);
+    const uint32_t n = s_scan[b.G];
+    for (uint64_t j = static_cast<uint64_t>(blockIdx.x) * kT + threadIdx.x; j < n; j += static_cast<uint64_t>(gridDim.x) * kT) {
+        const uint32_t c = static_cast<uint32_t>(region_entry(s_scan, b.G, b.R, static_cast<uint32_t>(j)));
+        const uint32_t nl = b.nlev()[c];
+        if (nl == kNlevRunning || !(nl & kNlevSky)) continue;
+        const Col col = background(sc, Ray{0.0, 0.0, 0.0, b.term(0)[c], b.term(1)[c], b.term(2)[c]});
+        b.term(0)[c] = col.r; b.term(1)[c] = col.g; b.term(2)[c] = col.b;
+        b.nlev()[c] = static_cast<uint8_t>(nl & ~kNlevSky);
+    }
+}
+
+// wf_sky_pixels, after the camera pass without compose: every chunk pixel whose camera ray missed
+// (csky) is finished here, in row order: the ray rebuilt from the FRAME coordinates (camera_ray:
+// tile origin, bands, the pass's AA sample), the skybox sampled, and the pixel written as the
+// average of its spp identical samples (main.rs:47-56) or, kAa, the sample added to its running sum.
+template <bool kAa>
+__global__ __launch_bounds__(kWfThreads) void wf_sky_pixels(DevScene sc, FrameParams fp, WfBufs b) {
+    __shared__ double s_srgb[255];
+    for (int i = threadIdx.x; i < 255; i += kWfThreads) s_srgb[i] = c_srgb_avg[i];
+    __syncthreads();
+    const uint64_t npix = static_cast<uint64_t>(fp.tile_w) * fp.rows;
+    for (uint64_t p = static_cast<uint64_t>(blockIdx.x) * kWfThreads + threadIdx.x; p < npix;
+         p += static_cast<uint64_t>(gridDim.x) * kWfThreads) {
+        if (!b.csky()[p]) continue;
+        const uint32_t lx = static_cast<uint32_t>(p % fp.tile_w), lrow = fp.row0 + static_cast<uint32_t>(p / fp.tile_w);
+        const Col c = background(sc, camera_ray(sc, fp, lx, lrow, fp.aa_pass));
+        if constexpr (kAa) aa_add(fp, static_cast<uint32_t>(p), aa_sample(c));
+        else write_pixel(fp, lx, lrow, average_samples(c, fp.spp), s_srgb);
+    }
+}
+
+hipError_t launch_sky_pixels(const DevScene& sc, const FrameParams& fp, const WfBufs& b, hipStream_t s, LaunchMarks* m) {
+    hipError_t e;
+    if (m && (e = m->begin(s)) != hipSuccess) return e;
+    const uint64_t npix = static_cast<uint64_t>(fp.tile_w) * fp.rows;
+    const dim3 grid(std::max(1u, static_cast<uint32_t>(std::min<uint64_t>(4u * b.G, (npix + kWfThreads - 1) / kWfThreads))));
+    if (fp.aa_acc) hipLaunchKernelGGL(wf_sky_pixels<true>, grid, dim3(kWfThreads), 0, s, sc, fp, b);
+    else hipLaunchKernelGGL(wf_sky_pixels<false>, grid, dim3(kWfThreads), 0, s, sc, fp, b);
+    return m ? m->mark(s, kKfCompose) : hipGetLastError();
+}
+
 hipError_t launch_fold(const DevScene& sc, const FrameParams& fp, const WfBufs& b, hipStream_t s, LaunchMarks* m,
                        uint32_t lo, uint32_t hi) {
     hipError_t e;
+    if (sc.skybox) {                           // the terminals of the chains that ended on a miss
+        if (m && (e = m->begin(s)) != hipSuccess) return e;
+        hipLaunchKernelGGL(wf_sky_term, dim3(b.G * (kWfThreads / RT_FOLD_THREADS)), dim3(RT_FOLD_THREADS), 0, s, sc, b);
+        if (m && (e = m->mark(s, kKfCompose)) != hipSuccess) return e;
+    }
     if (m && (e = m->begin(s)) != hipSuccess) return e;
     const dim3 grid(b.G * (kWfThreads / RT_FOLD_THREADS)), block(RT_FOLD_THREADS);
     if (fp.aa_acc) {                           // RT_ALGO_WAVEFRONT_AA: the sample's colour to the running sums
@@ -1264,7 +1348,10 @@ __device__ __forceinline__ bool bgr_dwords(const FrameParams& fp) {
 // consecutive addresses -- from the pixel map (chain, background or ambient
 // object) and the chains' colours in ccol.  The colours are the fold's /
 // write_pixel's values: f32 of the averaged f64 colour and to_srgb of it.
+// kSky (a skybox scene): a background pixel is not a constant: its camera ray is rebuilt from the
+// frame coordinates (camera_ray) and the skybox sampled in its direction.
 constexpr int kComposeWaves = kWfThreads / 64;
+template <bool kSky>
 __global__ __launch_bounds__(kWfThreads) void wf_compose(DevScene sc, FrameParams fp, WfBufs b) {
     __shared__ float s_rgb[kComposeWaves][192];
     __shared__ uint32_t s_bgr[kComposeWaves][48];
@@ -1284,7 +1371,12 @@ __global__ __launch_bounds__(kWfThreads) void wf_compose(DevScene sc, FrameParam
         uint32_t q = 0;
         if (lane < nv) {
             const uint32_t code = ldn(&b.pmap()[static_cast<size_t>(lrow) * fp.tile_w + x]);
-            if (code == kPixBackground) {
+            if (code == kPixBackground && kSky) {
+                const Col res = average_samples(background(sc, camera_ray(sc, fp, x, fp.row0 + lrow, fp.aa_pass)), fp.spp);
+                r = static_cast<float>(res.r); g = static_cast<float>(res.g); bl = static_cast<float>(res.b);
+                q = static_cast<uint32_t>(to_srgb(res.b, s_srgb)) | (static_cast<uint32_t>(to_srgb(res.g, s_srgb)) << 8) |
+                    (static_cast<uint32_t>(to_srgb(res.r, s_srgb)) << 16);
+            } else if (code == kPixBackground) {
                 r = fp.bg_rgb[0]; g = fp.bg_rgb[1]; bl = fp.bg_rgb[2];
                 q = fp.bg_bgr[0] | (static_cast<uint32_t>(fp.bg_bgr[1]) << 8) | (static_cast<uint32_t>(fp.bg_bgr[2]) << 16);
             } else if (code & kPixAmbient) {                           // (rare) the ambient colour of a camera hit
@@ -1306,6 +1398,7 @@ __global__ __launch_bounds__(kWfThreads) void wf_compose(DevScene sc, FrameParam
 // running sums.  Row by row, 64 consecutive pixels per wave: the pass's sample colour of each
 // pixel from the pixel map (the background's, an ambient end's, or the chain's, which the fold
 // left in term[chain]) is added to the pixel's running sum (aa_add: coalesced).
+template <bool kSky>
 __global__ __launch_bounds__(kWfThreads) void wf_aa_compose(DevScene sc, FrameParams fp, WfBufs b) {
     const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
     const uint32_t segs = (fp.tile_w + 63u) / 64u;
@@ -1317,7 +1410,8 @@ __global__ __launch_bounds__(kWfThreads) void wf_aa_compose(DevScene sc, FramePa
         const uint32_t p = lrow * fp.tile_w + x;
         const uint32_t code = ldn(&b.pmap()[p]);
         Col s;
-        if (code == kPixBackground) s = Col{fp.aa_bg[0], fp.aa_bg[1], fp.aa_bg[2]};
+        if (code == kPixBackground && kSky) s = aa_sample(background(sc, camera_ray(sc, fp, x, fp.row0 + lrow, fp.aa_pass)));
+        else if (code == kPixBackground) s = Col{fp.aa_bg[0], fp.aa_bg[1], fp.aa_bg[2]};
         else if (code & kPixAmbient) s = aa_sample(end_colour(sc, static_cast<int32_t>(code & ~kPixAmbient)));
         else s = Col{ldn(&b.term(0)[code]), ldn(&b.term(1)[code]), ldn(&b.term(2)[code])};
         aa_add(fp, p, s);
@@ -1483,7 +1577,10 @@ hipError_t launch_trace_frame(const DevScene& sc, const FrameParams& fp, int mod
     dim3 grid((fp.tile_w + 15) / 16, (fp.rows + 15) / 16);
     if (mode == 1) {
         size_t lds = static_cast<size_t>(sc.n_spheres) * sizeof(DevSphere);
-        hipLaunchKernelGGL(trace_frame_kernel<true>, grid, dim3(kBlock), lds, stream, sc, fp);
+        if (sc.skybox) hipLaunchKernelGGL((trace_frame_kernel<true, true>), grid, dim3(kBlock), lds, stream, sc, fp);
+        else hipLaunchKernelGGL(trace_frame_kernel<true>, grid, dim3(kBlock), lds, stream, sc, fp);
+    } else if (sc.skybox) {
+        hipLaunchKernelGGL((trace_frame_kernel<false, true>), grid, dim3(kBlock), 0, stream, sc, fp);
     } else {
         hipLaunchKernelGGL(trace_frame_kernel<false>, grid, dim3(kBlock), 0, stream, sc, fp);
     }
@@ -1554,17 +1651,21 @@ hipError_t launch_generation(const DevScene& sc, const FrameParams& fp, const Wf
             return e;
         if (ws.ma && (e = ws.ma->begin(ws.a)) != hipSuccess) return e;
         const size_t lds_t = staged_bytes<kSrcBvhL8C>(sc) + queue_lds_bytes(b.G);
-#define RT_TAIL(FR, AA) hipLaunchKernelGGL((wf_tail<FR, kCount, AA>), dim3(ws.tail_wgs), block, lds_t, ws.a, sc, fp, b, k, ws.tail_width)
+#define RT_TAIL_S(FR, AA, SKY) hipLaunchKernelGGL((wf_tail<FR, kCount, AA, SKY>), dim3(ws.tail_wgs), block, lds_t, ws.a, sc, fp, b, k, ws.tail_width)
+#define RT_TAIL(FR, AA) do { if (sc.skybox) RT_TAIL_S(FR, AA, true); else RT_TAIL_S(FR, AA, false); } while (0)
         if (fp.aa_acc) { if (sc.has_fresnel) RT_TAIL(true, true); else RT_TAIL(false, true); }
         else if (sc.has_fresnel) RT_TAIL(true, false);
         else RT_TAIL(false, false);
 #undef RT_TAIL
+#undef RT_TAIL_S
         return ws.ma ? ws.ma->mark(ws.a, kKfTail) : hipGetLastError();
     }
     e = ws.ma ? ws.ma->begin(ws.a) : hipSuccess;
     if (e != hipSuccess) return e;
-#define RT_NEAR(S, CAM, FR, AA) hipLaunchKernelGGL((wf_nearest<S, CAM, kCount, FR, AA>), grid, block, \
-                                                   staged_bytes<S>(sc) + queue_lds_bytes(b.G), ws.a, sc, fp, b, k)
+    // a skybox scene's instantiations (kSky), the others are untouched
+#define RT_NEAR_S(S, CAM, FR, AA, SKY) hipLaunchKernelGGL((wf_nearest<S, CAM, kCount, FR, AA, SKY>), grid, block, \
+                                                          staged_bytes<S>(sc) + queue_lds_bytes(b.G), ws.a, sc, fp, b, k)
+#define RT_NEAR(S, CAM, FR, AA) do { if (sc.skybox) RT_NEAR_S(S, CAM, FR, AA, true); else RT_NEAR_S(S, CAM, FR, AA, false); } while (0)
     // the camera pass of RT_ALGO_WAVEFRONT_AA (fp.aa_acc): its own instantiations, the others are untouched
 #define RT_CAM(S) do {                                                                                          \
         if (fp.aa_acc) { if (sc.has_fresnel) RT_NEAR(S, true, true, true); else RT_NEAR(S, true, false, true); }  \
@@ -1578,6 +1679,7 @@ hipError_t launch_generation(const DevScene& sc, const FrameParams& fp, const Wf
     else RT_NEAR(kSrcN, false, false, false);
 #undef RT_CAM
 #undef RT_NEAR
+#undef RT_NEAR_S
     e = ws.ma ? ws.ma->mark(ws.a, k == 0 ? kKfCamera : kKfNearest) : hipSuccess;
     if (e != hipSuccess) return e;
     if (static_cast<uint32_t>(k) > fp.max_depth) return hipSuccess;    // no shade records past the cut-off
@@ -1626,6 +1728,8 @@ hipError_t launch_wavefront(const DevScene& sc, const FrameParams& fp, const WfB
         }
 #undef RT_GEN
         if (e != hipSuccess) return e;
+        // a skybox scene's camera misses (compose: wf_compose / wf_aa_compose write them)
+        if (k == 0 && sc.skybox && !b.compose && (e = launch_sky_pixels(sc, fp, b, ws.a, ws.ma)) != hipSuccess) return e;
         if (k == 0 && ws.sp_s) {               // every pixel without a chain is final now
             if ((e = hipEventRecord(ws.sp_cam, ws.a)) != hipSuccess) return e;
             if ((e = hipStreamWaitEvent(ws.sp_s, ws.sp_cam, 0)) != hipSuccess) return e;
@@ -1658,7 +1762,8 @@ hipError_t launch_wavefront(const DevScene& sc, const FrameParams& fp, const WfB
         // now, row by row); after the chunk's last pass wf_resolve writes the chunk's rows
         if (b.compose) {
             if (ws.ma && (e = ws.ma->begin(ws.a)) != hipSuccess) return e;
-            hipLaunchKernelGGL(wf_aa_compose, row_grid, dim3(kWfThreads), 0, ws.a, sc, fp, b);
+            if (sc.skybox) hipLaunchKernelGGL(wf_aa_compose<true>, row_grid, dim3(kWfThreads), 0, ws.a, sc, fp, b);
+            else hipLaunchKernelGGL(wf_aa_compose<false>, row_grid, dim3(kWfThreads), 0, ws.a, sc, fp, b);
             if (ws.ma && (e = ws.ma->mark(ws.a, kKfCompose)) != hipSuccess) return e;
         }
         if (fp.aa_pass + 1 == fp.aa_spp) {
@@ -1668,7 +1773,8 @@ hipError_t launch_wavefront(const DevScene& sc, const FrameParams& fp, const WfB
         }
     } else if (b.compose) {                  // the frame, row by row, once every chain has its colour
         if (ws.ma && (e = ws.ma->begin(ws.a)) != hipSuccess) return e;
-        hipLaunchKernelGGL(wf_compose, row_grid, dim3(kWfThreads), 0, ws.a, sc, fp, b);
+        if (sc.skybox) hipLaunchKernelGGL(wf_compose<true>, row_grid, dim3(kWfThreads), 0, ws.a, sc, fp, b);
+        else hipLaunchKernelGGL(wf_compose<false>, row_grid, dim3(kWfThreads), 0, ws.a, sc, fp, b);
         if (ws.ma && (e = ws.ma->mark(ws.a, kKfCompose)) != hipSuccess) return e;
     }
     if (ws.sp_s) {                           // the chain pixels' segments, packed in row order

@@ -299,6 +299,21 @@ def skybox_scene(paths, width=96, height=64, max_depth=4):
     return s
 
 
+def skybox_chain_scene(paths, width=96, height=64, max_depth=4):
+    """skybox_scene with chain classes only, so that every chain schedule renders it (DESIGN.md
+    §3.13): the Phong and the Fresnel mirror sphere, a second Fresnel sphere in place of the
+    Transparent one, a mirror-like ground plane, the point light and a directional light."""
+    s = SceneSpec(width=width, height=height, antialias=1, max_depth=max_depth, name="skychain",
+                  camera=dict(DEFAULT_CAMERA), skybox=list(paths))
+    s.sphere((-1.5, 1.0, -6.0), 1.0, phong((0.1, 0.1, 0.1), (0.8, 0.8, 0.8), 64.0, (0.0, 0.0, 0.0)))
+    s.sphere((1.5, 1.0, -6.0), 1.0, fresnel((0.2, 0.2, 0.3), (1.0, 1.0, 1.0), 32.0, (0.0, 0.0, 0.0), 1.5))
+    s.sphere((0.0, 2.5, -9.0), 1.5, fresnel((0.05, 0.05, 0.05), (0.9, 0.9, 0.9), 64.0, (0.01, 0.01, 0.02), 1.4))
+    s.plane((0.0, 0.0, 0.0), (0.0, 1.0, 0.0), phong((0.4, 0.4, 0.4), (0.5, 0.5, 0.5), 24.0, (0.01, 0.01, 0.01)))
+    s.point_light((-10.0, 10.0, 5.0), (0.8, 0.8, 0.8))
+    s.directional_light((0.3, -1.0, -0.2), (0.3, 0.3, 0.35))
+    return s
+
+
 def random_spheres(n, width, height, max_depth, seed, box_scale=1.0, name="rand", plane=False, view="default"):
     """C3/C4/C5 generator: centres U(x in [-8,8], y in [0.3,6], z in [-16,-2]) scaled by
     box_scale about (0, 0.3, -2); r in U[0.1,0.6]; Phong kd in U[0.1,0.9]^3,

@@ -5,9 +5,11 @@ Each input is the stderr of
     hipcc -O3 -std=c++17 --offload-arch=gfx950 -ffp-contract=off -fno-fast-math -Iinclude \\
           -Irust-raytrace_amd/csrc -c rust-raytrace_amd/csrc/trace_kernel.hip -o /dev/null \\
           -Rpass-analysis=kernel-resource-usage 2> LOG
-on one checkout.  Kernels are matched by demangled name (c++filt); a trailing `false` template
-argument of wf_nearest / wf_fold / wf_tail in the second build (a defaulted parameter the first
-build does not have) is dropped before matching.  Prints every kernel of the first build whose
+on one checkout (the same line on path_kernel.hip for the path kernel's pair).  Kernels are matched
+by demangled name (c++filt); a trailing `false` template argument of wf_nearest / wf_fold / wf_tail /
+trace_frame_kernel / wf_compose / wf_aa_compose in the second build (a parameter the first build
+does not have; a kernel the first build has as a plain function loses its `<false>`) is dropped
+before matching.  Prints every kernel of the first build whose
 VGPRs, AGPRs, scratch, LDS or occupancy differ in the second (exit status 1 if any), then the
 kernels only the second build has.
 
@@ -43,11 +45,13 @@ def parse(path):
 
 
 def first_build_name(n):
-    m = re.match(r"(wf_nearest|wf_fold|wf_tail)<(.*)>$", n)
+    m = re.match(r"(wf_nearest|wf_fold|wf_tail|trace_frame_kernel|wf_compose|wf_aa_compose)<(.*)>$", n)
     if not m:
         return n
     args = [a.strip() for a in m.group(2).split(",")]
-    return f"{m.group(1)}<{', '.join(args[:-1])}>" if args[-1] == "false" else None
+    if args[-1] != "false":
+        return None
+    return f"{m.group(1)}<{', '.join(args[:-1])}>" if len(args) > 1 else m.group(1)
 
 
 def main():
