@@ -18,6 +18,9 @@
  *                         main.rs:39-57 + raytrace.rs:270-276 (raytrace) + raytrace.rs:261-267
  *                         (ray_color) + raytrace.rs:30-67 (PhongMaterial::color) + scene.rs:247-249
  *                         (Scene::intersect) + shapes.rs:50-112 (Sphere/Plane::intersect)
+ *   rt_render_accumulate / rt_accum_resolve
+ *                         main.rs:47-56 split over calls: `res = res + raytrace(..)` for a range of the
+ *                         AA samples, and `res / antialias` + write_bgr whenever a frame is wanted
  *   rt_scene_set_skybox   scene.rs:174-188       SkyboxBackground { px, nx, py, ny, pz, nz }
  *   rt_texture_load       texture.rs:34-37       Texture::load (BMP and binary PPM here; the image crate decodes more)
  *   rt_to_srgb            color.rs:593-600       fn to_srgb (used by Color::write_bgr, color.rs:628-632)
@@ -54,7 +57,11 @@
 extern "C" {
 #endif
 
-/* 6: rt_algo gained RT_ALGO_WAVEFRONT_AA (one wavefront pass per jittered AA sample); tuning key
+/* 7: progressive rendering: rt_accum (a device-resident f64 accumulator of one tile) with
+ * rt_accum_create / destroy / samples / reset, rt_render_accumulate, rt_accum_resolve / resolve_host,
+ * rt_accum_download / upload, and the host-only rt_checkpoint_write / read.  No struct, enum value or
+ * tuning key changed.
+ * 6: rt_algo gained RT_ALGO_WAVEFRONT_AA (one wavefront pass per jittered AA sample); tuning key
  * aa_wavefront added.  No struct changed.
  * 5: rt_out_flags gained RT_OUT_FRAME_ROWS (rt_render writes a banded tile
  * straight into its rows of a whole-frame host buffer); rt_ctx_reserve added;
@@ -69,7 +76,7 @@ extern "C" {
  * 4: rt_abi_version() added; RT_KF_TAIL (RT_KF_COUNT 8).  A caller checks
  * rt_abi_version() == RT_ABI_VERSION of the header it was built against before
  * passing any struct; any change of a struct, enum value or tuning key bumps it. */
-#define RT_ABI_VERSION 6
+#define RT_ABI_VERSION 7
 
 enum rt_status {
     RT_OK = 0,
@@ -324,6 +331,73 @@ int rt_ctx_reserve(rt_ctx* ctx, const rt_render_opts* opts, int host, void* stre
  * or frees), rt_ctx_set_tuning (also of the keys that rebuild the streams) and
  * rt_scene_upload of another scene: the next render replaces them, nothing else. */
 int rt_ctx_stats(rt_ctx* ctx, rt_stats* stats);
+/* ---- progressive rendering (main.rs:47-56 split over calls) ----
+ * The reference's pixel is `res = BLACK; for _ in 0..antialias { res = res + raytrace(..) }; res / antialias`
+ * (main.rs:47-56).  An rt_accum keeps `res` of every pixel of one tile on the device between calls: f64
+ * running sums r, g, b (24 B per pixel, tile row-major) and the number of samples in them.  Every random draw
+ * is keyed by (seed, pixel, AA sample index, ..) and by nothing that depends on the sample count, and a sum
+ * is continued one sample at a time in sample order, so accumulating samples [0, k) and then [k, n) gives,
+ * bit for bit, the one-shot render with spp = n and RT_JITTER_RANDOM (RT_ALGO_PATH / RT_ALGO_WAVEFRONT_AA),
+ * and a resolve after k samples is exactly the one-shot render with spp = k.
+ *
+ * Lifetime: an accumulator belongs to the context it was created on.  Destroy it before the context, or
+ * after: rt_ctx_destroy frees the device memory of the accumulators still alive, and the only call valid
+ * on such an accumulator afterwards is rt_accum_destroy (every other answers RT_E_INVALID).  Like the
+ * context's other calls, an accumulator's are not thread-safe. */
+typedef struct rt_accum rt_accum;   /* f64 running sums r,g,b of one tile (24 B per pixel, tile row-major) + the number of samples in them */
+
+/* main.rs:47 `let mut res = BLACK` for every pixel of the tile: binds the accumulator to the options that
+ * define the image (width, height, x0, tile_w, y0, tile_h, band, band_stride, band_phase, max_depth, jitter,
+ * seed) and to the scene uploaded at this moment (RT_E_NOSCENE without one).  opts->spp, algo, flags and
+ * bgr_pitch are not bound.  After rt_scene_upload of another scene every call but rt_accum_samples,
+ * rt_accum_reset and rt_accum_destroy answers RT_E_INVALID until rt_accum_reset. */
+int rt_accum_create(rt_ctx* ctx, const rt_render_opts* opts, rt_accum** out);
+void rt_accum_destroy(rt_accum* acc);
+int rt_accum_samples(const rt_accum* acc, uint32_t* samples);
+/* main.rs:47 again: samples = 0, bound to the scene uploaded now.  Nothing is cleared: the first sample
+ * accumulated afterwards stores 0.0 + s_0 without reading. */
+int rt_accum_reset(rt_accum* acc);
+/* main.rs:48-55 for n_samples turns of the loop: traces samples [S, S + n_samples) of every tile pixel (S: the
+ * accumulator's count) and adds each to the pixel's sum, in sample order, one at a time: for S == 0 the first
+ * step stores 0.0 + s_0 (a -0.0 sample becomes +0.0, stale memory is never read), otherwise the sum is loaded,
+ * the samples added, the sum stored.  No division.  Then the count is S + n_samples.  Asynchronous on `stream`
+ * (NULL: the context's own), a render of the context, ordered on the device like every other; afterwards
+ * rt_ctx_stats gives this call's own rays, shadow_rays, pixels, chunks and traced_rays == rays.  Every
+ * sample is traced, also one sample or centre jitter.  algo: RT_ALGO_PATH (every class), RT_ALGO_WAVEFRONT_AA
+ * (chain classes, at most 32 lights: one wavefront pass per sample), RT_ALGO_AUTO (the path kernel, unless
+ * the scene is of chain classes with at most 32 lights and tuning aa_wavefront is 1); 1-4 -> RT_E_UNSUPPORTED.
+ * Consecutive calls may use different algorithms.  flags: RT_COUNT_WORK and RT_TIME_KERNELS only.
+ * n_samples 0: RT_OK, nothing rendered.  A count that would pass 2^31 -> RT_E_INVALID.  A refused call is no
+ * render: the statistics stay the previous render's. */
+int rt_render_accumulate(rt_ctx* ctx, rt_accum* acc, uint32_t n_samples, int32_t algo, uint32_t flags, void* stream);
+/* main.rs:56 `(res / antialias).write_bgr(..)` with antialias = the accumulator's count, whenever wanted:
+ * pixel = sum / (double)samples, rounded once to f32 (d_rgb, tile_h * tile_w * 3 floats) and quantised from
+ * the f64 value (d_bgr, tile_h rows of bgr_pitch bytes, 0 -> 3 * tile_w); NaN propagates.  Either buffer may
+ * be NULL.  Device buffers, asynchronous on `stream`, after the accumulates issued so far; the bytes of a row
+ * past its pixels are left as they are.  The accumulator is not modified.  samples == 0 -> RT_E_INVALID.
+ * Tile-shaped outputs only (no RT_OUT_FRAME_ROWS). */
+int rt_accum_resolve(rt_ctx* ctx, rt_accum* acc, uint32_t bgr_pitch, void* d_rgb, void* d_bgr, void* stream);
+/* The same into host buffers, synchronous; the bytes of a BGR row past its pixels are written as zero
+ * (BMP row padding, main.rs:42). */
+int rt_accum_resolve_host(rt_ctx* ctx, rt_accum* acc, uint32_t bgr_pitch, float* out_rgb, uint8_t* out_bgr);
+/* The sums (3 * tile_w * tile_h doubles; cap_doubles smaller -> RT_E_INVALID) and the count, to the host and
+ * back: with rt_checkpoint_write / read, main.rs:47-56 stopped in one process and continued in another.
+ * Synchronous.  rt_accum_upload replaces sums and count (n_doubles must be 3 * tile_w * tile_h; samples
+ * <= 2^31); samples 0 is rt_accum_reset. */
+int rt_accum_download(rt_ctx* ctx, rt_accum* acc, double* sums, size_t cap_doubles, uint32_t* samples);
+int rt_accum_upload(rt_ctx* ctx, rt_accum* acc, const double* sums, size_t n_doubles, uint32_t samples);
+/* host only, no device: the checkpoint file of a progressive render.  Little-endian: an 88-byte header
+ * (magic "RTAMDCKP", format version u32 = 1, then u32 width, height, x0, tile_w, y0, tile_h, band,
+ * band_stride, band_phase, max_depth, i32 jitter, u32 samples, u32 reserved = 0, u64 seed, u64 scene_hash,
+ * u64 pixels = tile_w * tile_h) followed by 3 * pixels f64 sums.  scene_hash: the caller's identification of the scene
+ * (the CLI: FNV-1a 64 of the scene text).  rt_checkpoint_write writes n_doubles == 3 * tile_w * tile_h sums
+ * (else RT_E_INVALID) to a temporary name beside `path` and renames it.  rt_checkpoint_read fills opts'
+ * bound fields (the others zero), scene_hash and samples, and, with sums != NULL, the sums (cap_doubles
+ * smaller than the file's -> RT_E_INVALID); sums NULL: header only.  RT_E_IO: the file cannot be opened;
+ * RT_E_INVALID: wrong magic or version, a truncated file, a pixel count that is not tile_w * tile_h, a size
+ * that would overflow.  Nothing of the file is trusted before it is checked. */
+int rt_checkpoint_write(const char* path, const rt_render_opts* opts, uint64_t scene_hash, uint32_t samples, const double* sums, size_t n_doubles);
+int rt_checkpoint_read(const char* path, rt_render_opts* opts, uint64_t* scene_hash, uint32_t* samples, double* sums, size_t cap_doubles);
 /* Diagnostic (device): the sphere test's division t = x / (2a) (shapes.rs:68,75)
  * computed as the device computes it (the per-ray reciprocal of 2a finished with
  * the division's own correction steps, DESIGN.md §4 "Division by 2a") -> fast[i],
@@ -352,6 +426,7 @@ enum rt_kernel_family {
     RT_KF_CAMERA = 5,       /* wf_nearest, generation 0 (camera rays) */
     RT_KF_COMPOSE = 6,      /* wf_compose: the row-ordered frame pass (tuning compose); RT_ALGO_WAVEFRONT_AA:
                                wf_resolve after a chunk's last pass (and wf_aa_compose per pass, tuning compose);
+                               accum_resolve of an rt_accum_resolve after an RT_TIME_KERNELS rt_render_accumulate;
                                skybox scenes: wf_sky_pixels after the camera pass (compose 0) and wf_sky_term
                                before each fold */
     RT_KF_TAIL = 7,         /* wf_tail: the fused generations >= tail_fuse */

@@ -130,6 +130,13 @@ hipError_t launch_sqrt_probe(const double* x, uint32_t n, double* fast, double* 
 // staged: binary BVH + spheres in LDS (path_lds_bytes(sc, true) must fit).
 size_t path_lds_bytes(const DevScene& sc, bool staged);
 int path_waves_per_simd();          // the path kernel's occupancy (its launch bounds)
-hipError_t launch_path(const DevScene& sc, const FrameParams& fp, const PathStack& st, bool staged, hipStream_t stream);
+// accumulate (rt_render_accumulate): the instantiations that add samples [fp.aa_pass, fp.aa_pass + fp.aa_spp) of
+// every pixel to the running sums in fp.aa_acc (tile row-major) and write no pixel.
+hipError_t launch_path(const DevScene& sc, const FrameParams& fp, const PathStack& st, bool staged, hipStream_t stream,
+                       bool accumulate = false);
+// rt_accum_resolve: the tile's pixels from its running sums (fp.aa_acc, 3 f64 per tile pixel, tile row-major) of
+// fp.aa_spp samples each: sum / samples, rounded once to f32 and quantised from the f64 value, written row by row
+// (fp.out_rgb / out_bgr, bgr_pitch, pad_end; rows [0, fp.rows)).  workgroups: the grid's upper bound.
+hipError_t launch_accum_resolve(const FrameParams& fp, uint32_t workgroups, hipStream_t s);
 
 }  // namespace rtamd

@@ -325,7 +325,12 @@ __device__ Col trace_path(const DevScene& sc, const BvhView& v, const FrameParam
 }
 
 // kNodes: 2 = binary BVH, spheres and object ids staged in LDS; 0 = read through the caches.
-template <int kNodes>
+// kAccum (rt_render_accumulate; instantiations of their own, the others are untouched): the launch
+// traces the fp.aa_spp samples [fp.aa_pass, fp.aa_pass + fp.aa_spp) of every pixel and continues
+// the pixel's running sum in fp.aa_acc (3 f64 per tile pixel) with them, one sample at a time in
+// sample order: from 0.0 when fp.aa_pass is 0 (nothing read), else from the stored sum; the group's
+// lane 0 stores the sum.  No division, no write_pixel.
+template <int kNodes, bool kAccum = false>
 __global__ __launch_bounds__(kPathBlock, RT_PATH_WAVES) void path_kernel(DevScene sc, FrameParams fp, PathStack st) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     double* s_srgb = reinterpret_cast<double*>(lds);
@@ -359,10 +364,17 @@ __global__ __launch_bounds__(kPathBlock, RT_PATH_WAVES) void path_kernel(DevScen
         const uint32_t y = fp.y0 + ((lr / fp.band) * fp.band_stride + fp.band_phase) * fp.band + lr % fp.band;
         const uint64_t kp = key_pixel(fp.seed, x, y);
         Col res{0.0, 0.0, 0.0};
-        for (uint32_t a0 = 0; a0 < fp.spp; a0 += G) {
-            const uint32_t a = a0 + gl;
+        // the samples of this launch: all fp.spp of the pixel, or (kAccum) aa_spp of them from aa_pass on
+        const uint32_t first = kAccum ? fp.aa_pass : 0u, count = kAccum ? fp.aa_spp : fp.spp;
+        double* sum = nullptr;
+        if constexpr (kAccum) {
+            sum = fp.aa_acc + 3 * (static_cast<size_t>(lr) * fp.tile_w + lx);
+            if (first) res = Col{sum[0], sum[1], sum[2]};
+        }
+        for (uint32_t a0 = 0; a0 < count; a0 += G) {
+            const uint32_t a = first + a0 + gl;
             Col r{0.0, 0.0, 0.0};                                      // raytrace.rs:270-276
-            if (a < fp.spp) {
+            if (a0 + gl < count) {
                 const uint64_t ka = key_child(kp, a);
                 const double jx = fp.jitter ? key_f64(ka, 0) : 0.5;   // x drawn before y (main.rs:51-52)
                 const double jy = fp.jitter ? key_f64(ka, 1) : 0.5;
@@ -378,15 +390,19 @@ __global__ __launch_bounds__(kPathBlock, RT_PATH_WAVES) void path_kernel(DevScen
             if (G == 1) {
                 res = Col{res.r + r.r, res.g + r.g, res.b + r.b};
             } else {
-                const uint32_t m = min(G, fp.spp - a0);
+                const uint32_t m = min(G, count - a0);
                 for (uint32_t j = 0; j < m; ++j) {                     // sample order
                     const int src = static_cast<int>(gbase + j);
                     res = Col{res.r + __shfl(r.r, src, 64), res.g + __shfl(r.g, src, 64), res.b + __shfl(r.b, src, 64)};
                 }
             }
         }
-        res = Col{res.r / aa, res.g / aa, res.b / aa};
-        if (gl == 0) write_pixel(fp, lx, lr, res, s_srgb);
+        if constexpr (kAccum) {
+            if (gl == 0) { sum[0] = res.r; sum[1] = res.g; sum[2] = res.b; }
+        } else {
+            res = Col{res.r / aa, res.g / aa, res.b / aa};
+            if (gl == 0) write_pixel(fp, lx, lr, res, s_srgb);
+        }
     }
     for (int off = 32; off > 0; off >>= 1) {
         rays += __shfl_xor(rays, off, 64);
@@ -409,12 +425,16 @@ size_t path_lds_bytes(const DevScene& sc, bool staged) {
     return b;
 }
 
-hipError_t launch_path(const DevScene& sc, const FrameParams& fp, const PathStack& st, bool staged, hipStream_t stream) {
+hipError_t launch_path(const DevScene& sc, const FrameParams& fp, const PathStack& st, bool staged, hipStream_t stream,
+                       bool accumulate) {
     const uint64_t npix = static_cast<uint64_t>(fp.tile_w) * fp.rows;
     const uint64_t want = (npix * fp.path_group + kPathBlock - 1) / kPathBlock;   // path_group lanes per pixel
     const dim3 grid(static_cast<uint32_t>(want < st.T / kPathBlock ? want : st.T / kPathBlock));
     if (grid.x == 0) return hipSuccess;
-    if (staged) hipLaunchKernelGGL(path_kernel<2>, grid, dim3(kPathBlock), path_lds_bytes(sc, true), stream, sc, fp, st);
+    if (accumulate) {                       // fp.aa_acc: the running sums; fp.aa_pass, fp.aa_spp: the samples
+        if (staged) hipLaunchKernelGGL((path_kernel<2, true>), grid, dim3(kPathBlock), path_lds_bytes(sc, true), stream, sc, fp, st);
+        else hipLaunchKernelGGL((path_kernel<0, true>), grid, dim3(kPathBlock), path_lds_bytes(sc, false), stream, sc, fp, st);
+    } else if (staged) hipLaunchKernelGGL(path_kernel<2>, grid, dim3(kPathBlock), path_lds_bytes(sc, true), stream, sc, fp, st);
     else hipLaunchKernelGGL(path_kernel<0>, grid, dim3(kPathBlock), path_lds_bytes(sc, false), stream, sc, fp, st);
     return hipGetLastError();
 }

@@ -10,6 +10,14 @@
 //   raytrace [--scene FILE] [--out FILE] [--width W] [--height H] [--spp N]
 //            [--max-depth D] [--gpus N] [--band ROWS] [--jitter random|center] [--seed N]
 //            [--algo auto|wavefront|wavefront-aa|path|lds|global]
+//            [--progressive K] [--checkpoint FILE]
+//
+// --progressive K: the frame's samples in steps of K (rt_render_accumulate; main.rs:47-56 split over
+// calls); after every step --out is rewritten (a temporary name, renamed) with the image of the samples
+// so far and "samples done/total" goes to stderr.  --checkpoint FILE: FILE is written after every step
+// (the running sums, rt_checkpoint_write); a run that finds FILE continues from it when its options and
+// the scene's hash (FNV-1a 64 of the scene text) match, and refuses otherwise.  Both are single-device.
+#include <algorithm>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -33,6 +41,8 @@ struct Args {
     int algo = RT_ALGO_AUTO;
     int jitter = RT_JITTER_RANDOM;     // main.rs:51-52 jitters every sample; --jitter center = parity mode
     unsigned long long seed = 1;       // keyed draws (the reference seeds from OS entropy, main.rs:43)
+    long progressive = 0;              // samples per step (0: one render)
+    std::string checkpoint;
 };
 
 bool parse_args(int argc, char** argv, Args& a) {
@@ -49,6 +59,8 @@ bool parse_args(int argc, char** argv, Args& a) {
         else if (k == "--gpus" && (v = val())) a.gpus = std::atoi(v);
         else if (k == "--band" && (v = val())) a.band = static_cast<unsigned>(std::atol(v));
         else if (k == "--seed" && (v = val())) a.seed = std::strtoull(v, nullptr, 0);
+        else if (k == "--progressive" && (v = val())) a.progressive = std::atol(v);
+        else if (k == "--checkpoint" && (v = val())) a.checkpoint = v;
         else if (k == "--jitter" && (v = val())) a.jitter = std::string(v) == "center" ? RT_JITTER_CENTER : RT_JITTER_RANDOM;
         else if (k == "--algo" && (v = val())) {
             std::string s = v;
@@ -58,11 +70,110 @@ bool parse_args(int argc, char** argv, Args& a) {
         } else {
             std::fprintf(stderr, "usage: raytrace [--scene FILE] [--out FILE] [--width W] [--height H] [--spp N]\n"
                                  "                [--max-depth D] [--gpus N] [--band ROWS] [--jitter random|center]\n"
-                                 "                [--seed N] [--algo auto|wavefront|wavefront-aa|path|lds|global]\n");
+                                 "                [--seed N] [--algo auto|wavefront|wavefront-aa|path|lds|global]\n"
+                                 "                [--progressive K] [--checkpoint FILE]\n");
             return false;
         }
     }
     return true;
+}
+
+uint64_t fnv1a64(const std::string& text) {
+    uint64_t h = 0xcbf29ce484222325ull;
+    for (unsigned char ch : text) h = (h ^ ch) * 0x100000001b3ull;
+    return h;
+}
+
+// --progressive / --checkpoint: one device, the whole frame in one accumulator, `total` samples in steps.
+int run_progressive(const Args& a, rt_scene* scene, const std::string& text, uint32_t W, uint32_t H, uint32_t total) {
+    uint32_t pitch = 0;
+    uint8_t hdr[122];
+    rt_bmp_header(hdr, W, H, &pitch);
+    rt_ctx* ctx = nullptr;
+    rt_accum* acc = nullptr;
+    auto done_with = [&](int code) {
+        rt_accum_destroy(acc);
+        rt_ctx_destroy(ctx);
+        return code;
+    };
+    if (rt_ctx_create(0, &ctx) != RT_OK) { std::printf("error: %s\n", rt_last_error(nullptr)); return 1; }
+    if (rt_scene_upload(ctx, scene) != RT_OK) { std::printf("error: %s\n", rt_last_error(ctx)); return done_with(1); }
+    rt_render_opts o;
+    rt_render_opts_default(&o, W, H);
+    o.max_depth = a.max_depth; o.jitter = a.jitter; o.seed = a.seed;
+    if (rt_accum_create(ctx, &o, &acc) != RT_OK) { std::printf("error: %s\n", rt_last_error(ctx)); return done_with(1); }
+    const uint64_t hash = fnv1a64(text);
+    const size_t n_doubles = static_cast<size_t>(W) * H * 3;
+    std::vector<double> sums;
+    uint32_t done = 0;
+    if (!a.checkpoint.empty()) {
+        sums.resize(n_doubles);
+        rt_render_opts co;
+        uint64_t ch = 0;
+        uint32_t cs = 0;
+        const int rc = rt_checkpoint_read(a.checkpoint.c_str(), &co, &ch, &cs, nullptr, 0);
+        if (rc == RT_OK) {
+            const uint32_t cband = co.band ? co.band : 1, cstride = co.band_stride ? co.band_stride : 1;
+            const bool same = co.width == W && co.height == H && co.x0 == 0 && co.tile_w == W && co.y0 == 0 && co.tile_h == H &&
+                              cband == 1 && cstride == 1 && co.band_phase == 0 && co.max_depth == o.max_depth &&
+                              co.jitter == o.jitter && co.seed == o.seed;
+            if (!same || ch != hash || cs > total) {
+                std::printf("error: checkpoint %s was written for %s: not resumed (remove it to start again)\n", a.checkpoint.c_str(),
+                            !same ? "other options" : ch != hash ? "another scene" : "fewer samples than it holds");
+                return done_with(1);
+            }
+            if (rt_checkpoint_read(a.checkpoint.c_str(), &co, &ch, &cs, sums.data(), sums.size()) != RT_OK ||
+                rt_accum_upload(ctx, acc, sums.data(), sums.size(), cs) != RT_OK) {
+                std::printf("error: checkpoint %s: %s\n", a.checkpoint.c_str(), rt_last_error(nullptr));
+                return done_with(1);
+            }
+            done = cs;
+            std::fprintf(stderr, "resuming %s at %u samples\n", a.checkpoint.c_str(), done);
+        } else if (rc != RT_E_IO) {
+            std::printf("error: checkpoint %s: %s\n", a.checkpoint.c_str(), rt_last_error(nullptr));
+            return done_with(1);
+        }
+    }
+    const uint32_t step = a.progressive > 0 ? static_cast<uint32_t>(std::min<long>(a.progressive, total)) : total;
+    std::vector<uint8_t> frame(static_cast<size_t>(pitch) * H, 0);
+    const std::string tmp = a.out + ".tmp";
+    uint64_t rays = 0;
+    double kms = 0;
+    auto t0 = std::chrono::steady_clock::now();
+    for (bool first = true; first || done < total; first = false) {
+        const uint32_t n = std::min(step, total - done);
+        rt_stats st{};
+        if (n && (rt_render_accumulate(ctx, acc, n, a.algo, 0, nullptr) != RT_OK || rt_ctx_stats(ctx, &st) != RT_OK)) {
+            std::printf("error: %s\n", rt_last_error(ctx));
+            return done_with(1);
+        }
+        done += n;
+        rays += st.rays;
+        kms += st.kernel_ms;
+        if (done == 0) break;
+        // the image of the samples so far, under a temporary name first: --out is always a whole image
+        if (rt_accum_resolve_host(ctx, acc, pitch, nullptr, frame.data()) != RT_OK) {
+            std::printf("error: %s\n", rt_last_error(ctx));
+            return done_with(1);
+        }
+        if (rt_write_bmp(tmp.c_str(), W, H, frame.data(), pitch) != RT_OK || std::rename(tmp.c_str(), a.out.c_str()) != 0) {
+            std::printf("error: cannot write %s\n", a.out.c_str());
+            return done_with(1);
+        }
+        if (!a.checkpoint.empty() && n) {
+            uint32_t cs = 0;
+            if (rt_accum_download(ctx, acc, sums.data(), sums.size(), &cs) != RT_OK ||
+                rt_checkpoint_write(a.checkpoint.c_str(), &o, hash, cs, sums.data(), sums.size()) != RT_OK) {
+                std::printf("error: checkpoint %s: %s\n", a.checkpoint.c_str(), rt_last_error(nullptr));
+                return done_with(1);
+            }
+        }
+        std::fprintf(stderr, "samples %u/%u\n", done, total);
+    }
+    const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    std::fprintf(stderr, "%ux%u spp=%u depth=%u gpus=1 progressive: %llu rays, kernels %.3f ms, wall %.3f s\n", W, H, done,
+                 a.max_depth, static_cast<unsigned long long>(rays), kms, sec);
+    return done_with(0);
 }
 
 }  // namespace
@@ -89,6 +200,16 @@ int main(int argc, char** argv) {
     int ndev = 0;
     rt_device_count(&ndev);
     if (ndev < 1) { std::printf("error: no GPU\n"); return 1; }
+    if (a.progressive > 0 || !a.checkpoint.empty()) {
+        if (a.gpus > 1) {
+            std::printf("error: --progressive and --checkpoint render on one device: not with --gpus %d\n", a.gpus);
+            return 2;
+        }
+        if (spp == 0) { std::printf("error: --spp is 0 and the scene's antialias is 0\n"); return 1; }
+        const int rc = run_progressive(a, scene, text, W, H, spp);
+        rt_scene_free(scene);
+        return rc;
+    }
     const int G = std::max(1, std::min(a.gpus, ndev));
     const uint32_t band = std::max(1u, a.band);
     uint32_t pitch = 0;

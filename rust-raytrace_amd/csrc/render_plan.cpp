@@ -51,6 +51,45 @@ int plan_algo(const SceneFacts& sf, int algo, int jitter, uint32_t spp, int* mod
     return RT_OK;
 }
 
+int plan_accumulate(const SceneFacts& sf, int algo, uint32_t flags, uint32_t first, uint32_t n, int aa_wavefront,
+                    AccumPlan* plan, const char** err) {
+    *plan = AccumPlan{};
+    if (flags & ~kAccumFlags) {
+        *err = "rt_render_accumulate takes RT_COUNT_WORK and RT_TIME_KERNELS only";
+        return RT_E_INVALID;
+    }
+    if (first > kAccumMaxSamples || n > kAccumMaxSamples - first) {
+        *err = "the accumulator's sample count would pass 2^31";
+        return RT_E_INVALID;
+    }
+    if (algo >= RT_ALGO_BRUTE_LDS && algo <= RT_ALGO_WAVEFRONT_BRUTE) {
+        *err = "an accumulating render traces every sample: RT_ALGO_PATH, RT_ALGO_WAVEFRONT_AA or RT_ALGO_AUTO";
+        return RT_E_UNSUPPORTED;
+    }
+    if (algo != RT_ALGO_AUTO && algo != RT_ALGO_PATH && algo != RT_ALGO_WAVEFRONT_AA) {
+        *err = "bad algo";
+        return RT_E_INVALID;
+    }
+    int m = algo;
+    if (m == RT_ALGO_AUTO) m = aa_wavefront != 0 && !sf.needs_path && sf.n_lights <= 32 ? RT_ALGO_WAVEFRONT_AA : RT_ALGO_PATH;
+    if (m == RT_ALGO_WAVEFRONT_AA) {
+        // the mode's own refusals (jitter and spp do not enter them)
+        int mode = m;
+        if (const int rc = plan_algo(sf, m, RT_JITTER_RANDOM, 2, &mode, err, 0); rc != RT_OK) return rc;
+        plan->passes = n;
+    }
+    plan->mode = m;
+    return RT_OK;
+}
+
+uint32_t plan_path_group(uint64_t npix, uint32_t samples, uint32_t T_full, int64_t override_g) {
+    uint32_t G = 1;
+    while (G < 64 && 2 * G <= samples && npix * G < T_full) G *= 2;
+    if (override_g) G = static_cast<uint32_t>(override_g);   // A/B override
+    if (G == 0 || (G & (G - 1)) || G > 64) G = 1;
+    return G;
+}
+
 SourcePair plan_sources(const SceneFacts& sf, const int64_t* tune, int mode) {
     SourcePair p;
     if (mode != RT_ALGO_WAVEFRONT) {

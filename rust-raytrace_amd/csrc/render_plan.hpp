@@ -42,6 +42,33 @@ inline bool plan_aa_passes(int mode, int jitter, uint32_t spp) {
     return mode == RT_ALGO_WAVEFRONT_AA && jitter != RT_JITTER_CENTER && spp > 1;
 }
 
+// ---- accumulating renders (rt_render_accumulate) ------------------------------------------
+// The schedule of a call that adds samples [S, S + n) to an accumulator's running sums.
+//   mode       RT_ALGO_PATH or RT_ALGO_WAVEFRONT_AA: the only algorithms that trace every sample.  RT_ALGO_AUTO is
+//              the path kernel unless the scene is of chain classes with at most 32 lights and aa_wavefront (the
+//              tuning key) is set; jitter and n do not enter: an accumulating render never averages identical samples
+//   passes     RT_ALGO_WAVEFRONT_AA: one chain pass per sample, forced: also for n == 1 and centre jitter
+//              (plan_aa_passes is not asked); pass i runs with aa_pass = S + i, the global sample index
+//   G          RT_ALGO_PATH: lanes per pixel, from this call's n (plan_path_group), not from a total
+//   sparse     never: no pixel is final in an accumulating render
+//   resolve    never per chunk: the sums are resolved by rt_accum_resolve, whenever asked
+struct AccumPlan {
+    int mode = RT_ALGO_PATH;
+    uint32_t passes = 0;              // chain passes per chunk (0: the path kernel)
+    bool sparse = false, chunk_resolve = false;
+};
+// Flags an accumulating call accepts: RT_COUNT_WORK | RT_TIME_KERNELS.
+constexpr uint32_t kAccumFlags = RT_COUNT_WORK | RT_TIME_KERNELS;
+constexpr uint32_t kAccumMaxSamples = 1u << 31;
+// Returns RT_OK, or the status of a refusal with its text in *err: flags outside kAccumFlags and a count that would
+// pass 2^31 are RT_E_INVALID, algorithms 1-4 RT_E_UNSUPPORTED, an unknown algorithm RT_E_INVALID, and
+// RT_ALGO_WAVEFRONT_AA's own refusals (a path-only class, more than 32 lights) as plan_algo gives them.
+int plan_accumulate(const SceneFacts& sf, int algo, uint32_t flags, uint32_t first, uint32_t n, int aa_wavefront,
+                    AccumPlan* plan, const char** err);
+// The path kernel's lanes per pixel: enough work-items to fill the chip (T_full of them), at most one per sample of
+// the `samples` this launch traces per pixel; a power of two <= 64.  override_g: tuning path_group (0: none).
+uint32_t plan_path_group(uint64_t npix, uint32_t samples, uint32_t T_full, int64_t override_g);
+
 // ---- sphere sources ---------------------------------------------------------------------
 // (nearest, occlusion) sphere sources of a wavefront render, see launch_api.hpp; pfx2 / pfxq: the
 // nodes of the binary / quantised tree a prefix source stages in LDS (DevScene::pfx2 / pfxq, which

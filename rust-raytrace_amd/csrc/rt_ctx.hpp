@@ -1,7 +1,7 @@
 // The device context behind the C ABI (include/raytrace_amd.h), its error helpers, and what the
 // translation units that implement it share: rt_device.cpp (create / destroy, tuning, probes),
-// rt_scene_upload.cpp, rt_render.cpp (the render path, lanes, reserve, statistics) and rt_copy.cpp
-// (device -> host copies).
+// rt_scene_upload.cpp, rt_render.cpp (the render path, lanes, reserve, statistics), rt_accum.cpp
+// (progressive rendering: the accumulator and its calls) and rt_copy.cpp (device -> host copies).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -47,9 +47,30 @@ struct RenderReq {
     // rt_ctx_reserve: every allocation and stream the render would make, then warm_streams
     // instead of the launches; counters and the last render's statistics are left alone
     bool dry = false;
+    // rt_render_accumulate: the render adds samples [acc_first, acc_first + acc_n) of every tile pixel to the running
+    // sums at acc (3 f64 per tile pixel, tile row-major) and writes no pixel (render_plan.hpp, plan_accumulate)
+    bool accumulate = false;
+    double* acc = nullptr;             // (null: an empty tile)
+    uint32_t acc_first = 0, acc_n = 0;
 };
 
 }  // namespace rtamd
+
+// Progressive rendering (include/raytrace_amd.h): the running sums of one tile on the device and what they
+// are bound to.  Owned by the caller; its device memory by the context, which frees it when it is destroyed
+// first (ctx becomes null: only rt_accum_destroy is valid then).
+struct rt_accum {
+    rt_ctx* ctx = nullptr;
+    rt_render_opts o{};                // the bound options; spp, flags, algo and bgr_pitch are zero
+    uint64_t scene_gen = 0;            // rt_ctx::scene_gen at create / reset
+    double* d_sums = nullptr;          // 3 * npix f64, tile row-major (null: an empty tile)
+    uint64_t npix = 0;
+    uint32_t samples = 0;
+    bool timed = false;                // the last accumulate had RT_TIME_KERNELS: a resolve is timed too
+    // a device resolve reads the sums on a caller's stream: the next accumulate (which writes them) waits for it
+    hipEvent_t read_done = nullptr;
+    bool read_pending = false;
+};
 
 struct rt_ctx {
     int device = 0;
@@ -60,6 +81,8 @@ struct rt_ctx {
     size_t blob_bytes = 0;
     rtamd::DevScene dsc{};
     bool has_scene = false;
+    uint64_t scene_gen = 0;          // counts rt_scene_upload calls: what an rt_accum is bound to
+    std::vector<rt_accum*> accums;   // the accumulators alive on this context (rt_accum.cpp)
     bool deep_bvh4 = false;          // the 4-wide tree could overflow the traversal stack: binary tree only
     bool short_stack = false;        // binary tree fits the compact nearest-hit stack (16-bit codes, depth <= 32)
     bool short_stack18 = false;      // ... with 18-bit codes (the binary16 prefix source, src 6)
@@ -218,6 +241,13 @@ int warm_streams(rt_ctx* c, const std::vector<hipStream_t>& ss);
 // settled first (release_lane_memory).
 void drop_lanes(rt_ctx* c);
 int check_join_error(rt_ctx* c);
+// rt_render_accumulate behind its argument checks: one render of o's tile (o: the accumulator's bound options
+// with the call's algo and flags) that adds samples [first, first + n) to `sums`.  n == 0: the checks only.
+int render_accumulate(rt_ctx* c, const rt_render_opts* o, double* sums, uint32_t first, uint32_t n, void* stream);
+
+// ---- rt_accum.cpp -------------------------------------------------------------------------
+// rt_ctx_destroy: free the device memory of the accumulators still alive and detach them.
+void orphan_accums(rt_ctx* c);
 
 // ---- rt_copy.cpp --------------------------------------------------------------------------
 // Where rt_render puts a device row (RT_OUT_FRAME_ROWS or not): local row j of the tile, dev_pitch

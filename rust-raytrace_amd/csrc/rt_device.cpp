@@ -55,6 +55,7 @@ void rt_ctx_destroy(rt_ctx* c) {
     if (c->render_pending) (void)hipEventSynchronize(c->render_done);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     c->tally.on = false;                   // nobody can read it any more: drop_lanes has nothing to settle
+    orphan_accums(c);                      // accumulators still alive lose their sums; rt_accum_destroy stays valid
     if (c->d_blob) (void)hipFree(c->d_blob);
     if (c->d_counters) (void)hipFree(c->d_counters);
     if (c->d_srgb) (void)hipFree(c->d_srgb);

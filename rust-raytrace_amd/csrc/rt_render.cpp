@@ -424,11 +424,15 @@ int launch_chunks(rt_ctx* c, const rt_render_opts* o, RenderReq req, const Rende
         // RT_ALGO_WAVEFRONT_AA: the chunk's passes back to back on its lane (stream order and the
         // passes' own joins order a pixel's samples); the last one resolves the chunk's rows, and
         // only it records the lane's mark and the chunk's band event
-        const uint32_t passes = p.aa ? f.aa_spp : 1u;
+        // rt_render_accumulate: passes S .. S + n - 1 (aa_pass: the global sample index, so aa_add's "pass 0
+        // stores" is "the first sample stores") straight onto the accumulator's rows of the chunk (the sums
+        // are tile-wide; a chunk addresses them by its first row); aa_spp is 0, which no pass number + 1
+        // reaches: launch_wavefront never runs the per-chunk wf_resolve
+        const uint32_t passes = req.accumulate ? req.acc_n : p.aa ? f.aa_spp : 1u;
         for (uint32_t a = 0; a < passes; ++a) {
             const bool last = a + 1 == passes;
-            f.aa_pass = a;
-            f.aa_acc = p.aa ? L.acc : nullptr;
+            f.aa_pass = req.acc_first + a;
+            f.aa_acc = req.accumulate ? req.acc + 3 * static_cast<size_t>(f.row0) * f.tile_w : p.aa ? L.acc : nullptr;
             f.aa_flags = p.aa && last && ci + 1 == p.cp.n_chunks ? kAaTallyGens : 0u;
             WfStreams wp = ws;
             if (!last) wp.fold_ev = nullptr;
@@ -505,9 +509,14 @@ int render_wavefront(rt_ctx* c, const rt_render_opts* o, RenderReq req, const Re
     if (c->t(kTuneVerbose))
         std::fprintf(stderr, "rtamd: chunks %u x %u rows (first %u), lanes %d, G %u, R %u\n", p.cp.n_chunks, p.cp.chunk_rows,
                      p.cp.first_rows, p.cp.n_lanes, p.rg.G, p.rg.R);
-    if (aa && c->t(kTuneVerbose))
+    if (aa && !req.accumulate && c->t(kTuneVerbose))
         std::fprintf(stderr, "rtamd: aa passes %u, chunks %u x %u rows, resolve after each chunk's last pass, sums %s\n",
                      fp.aa_spp, p.cp.n_chunks, p.cp.chunk_rows, c->t(kTuneCompose) ? "row by row (compose)" : "per pixel");
+    if (req.accumulate && c->t(kTuneVerbose))
+        std::fprintf(stderr, "rtamd: accumulate samples [%u, %u) passes\n"
+                             "rtamd: aa passes %u, chunks %u x %u rows, no resolve (the accumulator keeps the sums), sums %s\n",
+                     req.acc_first, req.acc_first + req.acc_n, req.acc_n, p.cp.n_chunks, p.cp.chunk_rows,
+                     c->t(kTuneCompose) ? "row by row (compose)" : "per pixel");
     return launch_chunks(c, o, req, rcall, p);
 }
 
@@ -518,12 +527,15 @@ int render_path(rt_ctx* c, const rt_render_opts* o, RenderReq req, RenderCall& r
     const uint64_t npix = static_cast<uint64_t>(o->tile_w) * o->tile_h;
     // work-items per CU = the kernel's occupancy (4 SIMDs x waves per SIMD x 64 lanes)
     const uint32_t T_full = static_cast<uint32_t>(c->n_cu) * 256u * static_cast<uint32_t>(path_waves_per_simd());
-    // lanes per pixel: enough work-items to fill the chip, at most one per AA sample
-    uint32_t G = 1;
-    while (G < 64 && 2 * G <= rcall.spp && npix * G < T_full) G *= 2;
-    if (const int64_t ge = c->t(kTunePathGroup)) G = static_cast<uint32_t>(ge);   // A/B override
-    if (G == 0 || (G & (G - 1)) || G > 64) G = 1;
+    // lanes per pixel: enough work-items to fill the chip, at most one per AA sample (an accumulating
+    // render: per sample of this call)
+    const uint32_t G = plan_path_group(npix, req.accumulate ? req.acc_n : rcall.spp, T_full, c->t(kTunePathGroup));
     rcall.fp.path_group = G;
+    if (req.accumulate) {                // samples [aa_pass, aa_pass + aa_spp) onto the sums at aa_acc
+        rcall.fp.aa_pass = req.acc_first;
+        rcall.fp.aa_spp = req.acc_n;
+        rcall.fp.aa_acc = req.acc;
+    }
     const uint32_t T = static_cast<uint32_t>(std::min<uint64_t>(T_full, (npix * G + 255) / 256 * 256));
     PathStack ps{};
     ps.T = T;
@@ -541,12 +553,14 @@ int render_path(rt_ctx* c, const rt_render_opts* o, RenderReq req, RenderCall& r
     if (req.dry) return warm_streams(c, {st});
     if (const int rc = zero_counters(c, st); rc != RT_OK) return rc;
     const bool staged = path_lds_bytes(c->dsc, true) <= 48 * 1024;
+    if (req.accumulate && c->t(kTuneVerbose))
+        std::fprintf(stderr, "rtamd: accumulate samples [%u, %u) path\n", req.acc_first, req.acc_first + req.acc_n);
     if (c->t(kTuneVerbose))
         std::fprintf(stderr, "rtamd: path G %u T %u staged %d npix %llu\n", G, T, staged ? 1 : 0,
                      static_cast<unsigned long long>(npix));
     c->ev0_set = true;
     HIP_TRY(c, hipEventRecord(c->ev0, st));
-    HIP_TRY(c, launch_path(c->dsc, rcall.fp, ps, staged, st));
+    HIP_TRY(c, launch_path(c->dsc, rcall.fp, ps, staged, st, req.accumulate));
     return RT_OK;
 }
 
@@ -569,15 +583,22 @@ int render_device(rt_ctx* c, const rt_render_opts* o, void* d_rgb, void* d_bgr, 
     const SceneFacts sf = scene_facts(c);
     int mode = o->algo;
     const char* refusal = nullptr;
-    if ((rc = plan_algo(sf, o->algo, o->jitter, rcall.spp, &mode, &refusal, static_cast<int>(c->t(kTuneAaWavefront)))) != RT_OK)
+    AccumPlan ap;
+    if (req.accumulate) {        // rt_render_accumulate: its own rules (passes forced, every sample traced)
+        if ((rc = plan_accumulate(sf, o->algo, o->flags, req.acc_first, req.acc_n, static_cast<int>(c->t(kTuneAaWavefront)),
+                                  &ap, &refusal)) != RT_OK)
+            return fail(c, rc, refusal);
+        if (req.acc_n == 0) return RT_OK;                           // nothing to render
+        mode = ap.mode;
+    } else if ((rc = plan_algo(sf, o->algo, o->jitter, rcall.spp, &mode, &refusal, static_cast<int>(c->t(kTuneAaWavefront)))) != RT_OK)
         return fail(c, rc, refusal);
     // RT_ALGO_WAVEFRONT_AA: one pass of RT_ALGO_WAVEFRONT's schedule per AA sample, each a render of
     // one sample per pixel (its tally counts its own rays) that adds to the pixels' running sums;
     // with centre jitter or one sample it is RT_ALGO_WAVEFRONT's render
-    const bool aa = plan_aa_passes(mode, o->jitter, rcall.spp);
+    const bool aa = req.accumulate ? ap.passes > 0 : plan_aa_passes(mode, o->jitter, rcall.spp);
     if (mode == RT_ALGO_WAVEFRONT_AA) mode = RT_ALGO_WAVEFRONT;
     if (aa) {
-        rcall.fp.aa_spp = rcall.spp;
+        rcall.fp.aa_spp = req.accumulate ? 0u : rcall.spp;                 // (accumulating: nothing divides)
         rcall.fp.spp = 1;
         for (int k = 0; k < 3; ++k) rcall.fp.aa_bg[k] = (0.0 + c->dsc.bg[k]) / 1.0;   // raytrace.rs:270-276, one camera sample
     }
@@ -716,6 +737,15 @@ int warm_streams(rt_ctx* c, const std::vector<hipStream_t>& ss) {
     for (hipStream_t s : ss)
         if (s) HIP_TRY(c, hipStreamSynchronize(s));
     return RT_OK;
+}
+
+int render_accumulate(rt_ctx* c, const rt_render_opts* o, double* sums, uint32_t first, uint32_t n, void* stream) {
+    RenderReq req;
+    req.accumulate = true;
+    req.acc = sums;
+    req.acc_first = first;
+    req.acc_n = n;
+    return render_device(c, o, nullptr, nullptr, stream, req);
 }
 
 void drop_lanes(rt_ctx* c) {

@@ -430,6 +430,7 @@ static int scene_upload(rt_ctx* c, const rt_scene* s) {
     for (const DevLightGrid& g : lg.grids) c->all_lights_gridded = c->all_lights_gridded && g.R > 0;
     c->scene_spp = s->antialias;
     c->has_scene = true;
+    ++c->scene_gen;                   // accumulators bound to the previous scene refuse until reset
     return RT_OK;
 }
 

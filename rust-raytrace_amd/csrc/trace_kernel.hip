@@ -1449,6 +1449,39 @@ __global__ __launch_bounds__(kWfThreads) void wf_resolve(FrameParams fp) {
     }
 }
 
+// rt_accum_resolve: main.rs:56 for an accumulator's tile, whenever asked.  sums: the tile pixels'
+// running sums (3 f64 per pixel, tile row-major) of `samples` samples each; a pixel is sum /
+// (double)samples (NaN propagates), rounded once to f32 and quantised from the f64 value.  Row
+// by row over rows [0, fp.rows), 64 consecutive pixels per wave, coalesced through
+// store_row_segment as wf_resolve and wf_compose write a frame.  Reads the sums, never writes them.
+__global__ __launch_bounds__(kWfThreads) void accum_resolve(FrameParams fp, const double* sums, uint32_t samples) {
+    __shared__ float s_rgb[kComposeWaves][192];
+    __shared__ uint32_t s_bgr[kComposeWaves][48];
+    __shared__ double s_srgb[255];
+    for (int i = threadIdx.x; i < 255; i += kWfThreads) s_srgb[i] = c_srgb_avg[i];
+    __syncthreads();
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+    const uint32_t segs = (fp.tile_w + 63u) / 64u;
+    const uint64_t total = static_cast<uint64_t>(segs) * fp.rows;
+    const bool dw = bgr_dwords(fp);
+    const double aa = static_cast<double>(samples);
+    for (uint64_t sg = static_cast<uint64_t>(blockIdx.x) * kComposeWaves + wave; sg < total;
+         sg += static_cast<uint64_t>(gridDim.x) * kComposeWaves) {     // wave-uniform
+        const uint32_t lrow = static_cast<uint32_t>(sg / segs), x0 = static_cast<uint32_t>(sg % segs) * 64u;
+        const uint32_t nv = min(64u, fp.tile_w - x0);
+        float r = 0.0f, g = 0.0f, bl = 0.0f;
+        uint32_t q = 0;
+        if (lane < nv) {
+            const double* a = sums + 3 * (static_cast<size_t>(lrow) * fp.tile_w + x0 + lane);
+            const Col res{ldn(&a[0]) / aa, ldn(&a[1]) / aa, ldn(&a[2]) / aa};
+            r = static_cast<float>(res.r); g = static_cast<float>(res.g); bl = static_cast<float>(res.b);
+            q = static_cast<uint32_t>(to_srgb(res.b, s_srgb)) | (static_cast<uint32_t>(to_srgb(res.g, s_srgb)) << 8) |
+                (static_cast<uint32_t>(to_srgb(res.r, s_srgb)) << 16);
+        }
+        store_row_segment(fp, s_rgb[wave], s_bgr[wave], dw, lrow, x0, nv, r, g, bl, q);
+    }
+}
+
 // Scene::intersect calls of this chunk: every pixel's camera ray, every later
 // queue entry, and one shadow query per light per shade record; plus the
 // per-generation queue sizes.  One workgroup; atomics because chunks on
@@ -1788,6 +1821,14 @@ hipError_t launch_wavefront(const DevScene& sc, const FrameParams& fp, const WfB
 
 hipError_t launch_tally(const FrameParams& fp, const WfBufs& b, int n_lights, int generations, hipStream_t s) {
     hipLaunchKernelGGL(wf_tally, dim3(1), dim3(kWfThreads), 0, s, fp, b, n_lights, generations);
+    return hipGetLastError();
+}
+
+hipError_t launch_accum_resolve(const FrameParams& fp, uint32_t workgroups, hipStream_t s) {
+    const uint64_t segs = static_cast<uint64_t>((fp.tile_w + 63u) / 64u) * fp.rows;
+    if (segs == 0) return hipSuccess;
+    const dim3 grid(std::max(1u, static_cast<uint32_t>(std::min<uint64_t>(workgroups, (segs + kComposeWaves - 1) / kComposeWaves))));
+    hipLaunchKernelGGL(accum_resolve, grid, dim3(kWfThreads), 0, s, fp, fp.aa_acc, fp.aa_spp);
     return hipGetLastError();
 }
 

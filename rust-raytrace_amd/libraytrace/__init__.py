@@ -20,7 +20,7 @@ PKG_DIR = os.path.dirname(_HERE)
 LIB_PATH = os.environ.get("RT_LIBRTAMD") or os.path.join(PKG_DIR, "librtamd.so")
 HEADER_PATH = os.path.join(os.path.dirname(PKG_DIR), "include", "raytrace_amd.h")
 
-RT_ABI_VERSION = 6               # include/raytrace_amd.h
+RT_ABI_VERSION = 7               # include/raytrace_amd.h
 RT_OK = 0
 RT_E_INVALID, RT_E_NODEVICE, RT_E_HIP, RT_E_NOMEM = -1, -2, -3, -4
 RT_E_UNSUPPORTED, RT_E_PARSE, RT_E_NOSCENE, RT_E_IO = -5, -6, -7, -8
@@ -119,6 +119,19 @@ def _load():
         "rt_render_device": (C.c_int, [C.c_void_p, P(rt_render_opts), C.c_void_p, C.c_void_p, C.c_void_p]),
         "rt_ctx_reserve": (C.c_int, [C.c_void_p, P(rt_render_opts), C.c_int, C.c_void_p]),
         "rt_ctx_stats": (C.c_int, [C.c_void_p, P(rt_stats)]),
+        "rt_accum_create": (C.c_int, [C.c_void_p, P(rt_render_opts), P(C.c_void_p)]),
+        "rt_accum_destroy": (None, [C.c_void_p]),
+        "rt_accum_samples": (C.c_int, [C.c_void_p, P(C.c_uint32)]),
+        "rt_accum_reset": (C.c_int, [C.c_void_p]),
+        "rt_render_accumulate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, C.c_uint32, C.c_void_p]),
+        "rt_accum_resolve": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
+        "rt_accum_resolve_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, P(C.c_float), P(C.c_uint8)]),
+        "rt_accum_download": (C.c_int, [C.c_void_p, C.c_void_p, P(C.c_double), C.c_size_t, P(C.c_uint32)]),
+        "rt_accum_upload": (C.c_int, [C.c_void_p, C.c_void_p, P(C.c_double), C.c_size_t, C.c_uint32]),
+        "rt_checkpoint_write": (C.c_int, [C.c_char_p, P(rt_render_opts), C.c_uint64, C.c_uint32, P(C.c_double),
+                                          C.c_size_t]),
+        "rt_checkpoint_read": (C.c_int, [C.c_char_p, P(rt_render_opts), P(C.c_uint64), P(C.c_uint32), P(C.c_double),
+                                         C.c_size_t]),
         "rt_ctx_generation_counts": (C.c_int, [C.c_void_p, P(C.c_uint32), P(C.c_uint32), C.c_int]),
         "rt_ctx_kernel_times": (C.c_int, [C.c_void_p, P(C.c_double), P(C.c_uint32), C.c_int]),
         "rt_light_grid_candidates": (C.c_int, [C.c_void_p, C.c_int, C.c_int, P(C.c_double), C.c_uint32,
@@ -480,6 +493,11 @@ class Context:
                self._h)
         return fast, slow
 
+    def accumulator(self, opts):
+        """rt_accum_create: a progressive render of opts' tile (main.rs:47-56 split over calls), bound to
+        opts' image-defining fields and to the scene uploaded now."""
+        return Accumulator(self, opts)
+
     def kernel_times(self):
         """{family: (summed ms, launches)} over the RT_TIME_KERNELS renders since
         the previous call (then reset); synchronises with the last timed launch."""
@@ -505,6 +523,107 @@ class Context:
             self.close()
         except Exception:
             pass
+
+
+class Accumulator:
+    """rt_accum: the f64 running sums of one tile on the device and the number of samples in them.
+    add(n) traces samples [samples, samples + n) and adds them in sample order; resolve() gives the
+    image of the samples so far (sum / samples), as often as wanted.  Close it before its Context, or
+    after (then only close() does anything)."""
+
+    def __init__(self, ctx, opts):
+        self._ctx = ctx
+        h = C.c_void_p()
+        _check(lib.rt_accum_create(ctx._h, C.byref(opts), C.byref(h)), ctx._h)
+        self._h = h
+        self.tile_w, self.tile_h = opts.tile_w, opts.tile_h
+
+    @property
+    def samples(self):
+        n = C.c_uint32()
+        _check(lib.rt_accum_samples(self._h, C.byref(n)))
+        return n.value
+
+    def add(self, n, algo=RT_ALGO_AUTO, flags=0, stream_ptr=None):
+        """rt_render_accumulate (asynchronous; Context.stats() gives this call's own statistics)."""
+        _check(lib.rt_render_accumulate(self._ctx._h, self._h, int(n), int(algo), int(flags), C.c_void_p(stream_ptr or 0)),
+               self._ctx._h)
+
+    def resolve(self, rgb=True, bgr=True, pitch=0):
+        """rt_accum_resolve_host -> (rgb float32 [tile_h, tile_w, 3] or None, bgr uint8 [tile_h, pitch] or None)."""
+        p = pitch or 3 * self.tile_w
+        out_rgb = np.zeros((self.tile_h, self.tile_w, 3), np.float32) if rgb else None
+        out_bgr = np.full((self.tile_h, p), 0xCD, np.uint8) if bgr else None
+        _check(lib.rt_accum_resolve_host(self._ctx._h, self._h, int(pitch),
+                                         out_rgb.ctypes.data_as(C.POINTER(C.c_float)) if rgb else None,
+                                         out_bgr.ctypes.data_as(C.POINTER(C.c_uint8)) if bgr else None), self._ctx._h)
+        return out_rgb, out_bgr
+
+    def resolve_device(self, d_rgb_ptr, d_bgr_ptr, pitch=0, stream_ptr=None):
+        """rt_accum_resolve into device buffers (raw pointers), asynchronous."""
+        _check(lib.rt_accum_resolve(self._ctx._h, self._h, int(pitch), C.c_void_p(d_rgb_ptr or 0), C.c_void_p(d_bgr_ptr or 0),
+                                    C.c_void_p(stream_ptr or 0)), self._ctx._h)
+
+    def reset(self):
+        _check(lib.rt_accum_reset(self._h), self._ctx._h)
+
+    def download(self, cap=None):
+        """rt_accum_download -> (sums float64 [tile_h, tile_w, 3], samples); cap: the capacity passed (a test's)."""
+        sums = np.zeros((self.tile_h, self.tile_w, 3), np.float64)
+        n = C.c_uint32()
+        _check(lib.rt_accum_download(self._ctx._h, self._h, sums.ctypes.data_as(C.POINTER(C.c_double)),
+                                     sums.size if cap is None else int(cap), C.byref(n)), self._ctx._h)
+        return sums, n.value
+
+    def upload(self, sums, samples):
+        arr = np.ascontiguousarray(sums, dtype=np.float64)
+        _check(lib.rt_accum_upload(self._ctx._h, self._h, arr.ctypes.data_as(C.POINTER(C.c_double)), arr.size, int(samples)),
+               self._ctx._h)
+
+    def close(self):
+        if self._h:
+            lib.rt_accum_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def checkpoint_write(path, opts, scene_hash, samples, sums):
+    """rt_checkpoint_write (host only): the bound fields of opts, scene_hash, samples and the sums to `path`."""
+    arr = np.ascontiguousarray(sums, dtype=np.float64)
+    _check(lib.rt_checkpoint_write(os.fsencode(path), C.byref(opts), int(scene_hash), int(samples),
+                                   arr.ctypes.data_as(C.POINTER(C.c_double)), arr.size))
+
+
+def checkpoint_read(path, header_only=False):
+    """rt_checkpoint_read -> (opts, scene_hash, samples, sums float64 [tile_h, tile_w, 3] or None)."""
+    o = rt_render_opts()
+    h, n = C.c_uint64(), C.c_uint32()
+    _check(lib.rt_checkpoint_read(os.fsencode(path), C.byref(o), C.byref(h), C.byref(n), None, 0))
+    if header_only:
+        return o, h.value, n.value, None
+    sums = np.zeros((o.tile_h, o.tile_w, 3), np.float64)
+    _check(lib.rt_checkpoint_read(os.fsencode(path), C.byref(o), C.byref(h), C.byref(n),
+                                  sums.ctypes.data_as(C.POINTER(C.c_double)), sums.size))
+    return o, h.value, n.value, sums
+
+
+def scene_hash(text):
+    """FNV-1a 64 of the scene text: what the CLI's --checkpoint binds a checkpoint to."""
+    h = 0xcbf29ce484222325
+    for b in (text.encode() if isinstance(text, str) else bytes(text)):
+        h = ((h ^ b) * 0x100000001b3) & 0xFFFFFFFFFFFFFFFF
+    return h
 
 
 def header_functions():
