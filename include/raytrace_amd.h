@@ -57,7 +57,9 @@
 extern "C" {
 #endif
 
-/* 7: progressive rendering: rt_accum (a device-resident f64 accumulator of one tile) with
+/* 8: rt_cull_check and rt_cull_reach added (diagnostics of the conservative f32 culling and of the
+ * far-origin rule).  No struct, enum value or tuning key changed.
+ * 7: progressive rendering: rt_accum (a device-resident f64 accumulator of one tile) with
  * rt_accum_create / destroy / samples / reset, rt_render_accumulate, rt_accum_resolve / resolve_host,
  * rt_accum_download / upload, and the host-only rt_checkpoint_write / read.  No struct, enum value or
  * tuning key changed.
@@ -76,7 +78,7 @@ extern "C" {
  * 4: rt_abi_version() added; RT_KF_TAIL (RT_KF_COUNT 8).  A caller checks
  * rt_abi_version() == RT_ABI_VERSION of the header it was built against before
  * passing any struct; any change of a struct, enum value or tuning key bumps it. */
-#define RT_ABI_VERSION 7
+#define RT_ABI_VERSION 8
 
 enum rt_status {
     RT_OK = 0,
@@ -409,6 +411,26 @@ int rt_div_a2_check(rt_ctx* ctx, const double* x, const double* a, uint32_t n, d
  * DESIGN.md §4) -> fast[i], and the device's own sqrt -> slow[i].  Tests compare
  * both with IEEE sqrt bit for bit.  Synchronous. */
 int rt_sqrt_check(rt_ctx* ctx, const double* x, uint32_t n, double* fast, double* slow);
+/* Diagnostic (device): the conservative f32 culling arithmetic of the tree walks ("BVH
+ * exactness" items 2, 3 and 6), computed by the functions the traversal kernels call, for n records.
+ * Record i: rays[6 i ..] = ray origin and direction (f64); boxes[6 i ..] = box lo x, y, z, hi x, y, z
+ * (f32); t[i] = a hit distance >= 0, or +inf for none; codes[i] = a node index or leaf code.  reach:
+ * the culling domain a scene would carry (rt_cull_reach, an f32 value; +inf: every origin inside).  Outputs, 5 per
+ * record: out_i = { the slab tests' exponent te (they run on t 2^te); the slab test's verdict (0 / 1)
+ * with the limit out_f[0]; the verdict of the form the whole-LDS walk runs (near / far bounds); the
+ * code read back from a 16-bit compact stack entry made of (codes[i], out_f[1]); from an 18-bit one };
+ * out_f = { the f32 limit for t[i] in scaled t (>= t 2^te); the slab test's widened entry t; the near /
+ * far form's; the entry t read back from the 16-bit compact entry; from the 18-bit one }.  A ray whose
+ * origin lies beyond reach on some axis (finite as f32) reports both verdicts 1 and entry t 0 for
+ * every finite box: the far-origin rule.  Tests compare with exact arithmetic on the host
+ * (tests/test_gpu_culling.py).  Synchronous. */
+int rt_cull_check(rt_ctx* ctx, uint32_t n, const double* rays, const float* boxes, const double* t, const int32_t* codes,
+                  double reach, int32_t* out_i, float* out_f);
+/* host only: the culling domain of a scene whose spheres' largest finite |centre +- radius| is extent,
+ * 32 (1 + extent) rounded down to f32: rays, shade points and cameras whose f32-rounded coordinates lie
+ * within it on every axis are culled through the padded boxes, the others test every sphere (DESIGN.md
+ * 4, "the far-origin rule"). */
+double rt_cull_reach(double extent);
 /* Queue sizes of the last wavefront chunk (RT_ALGO_WAVEFRONT_AA: of its last pass): queue[k] = rays traced at depth k
  * (generation 0: 0, the camera rays are not queued), shaded[k] = hits that
  * issued shadow queries.  Diagnostic. */

@@ -75,6 +75,6 @@ LightGridResult build_light_grids(const std::vector<DevSphere>& spheres, const s
 LightGridResult build_view_grid(const std::vector<DevSphere>& spheres, const std::vector<double>& r_leaf,
                                 const double pos[3], double pad, int R, size_t max_entries);
 // Host mirror of the device's candidate list (test / diagnostic).
-bool light_grid_candidates(const LightGridResult& lg, int light, const double p[3], std::vector<int32_t>& out);
+bool light_grid_candidates(const LightGridResult& lg, int light, const double p[3], float reach, std::vector<int32_t>& out);
 
 }  // namespace rtamd

@@ -135,6 +135,29 @@ struct DevLgEntry {
     float near;
 };
 
+// The culling domain ("the far-origin rule").  A sphere's padded box holds every
+// hit the f64 quadratic can report only for a ray that starts within kCullReach * (1 + E) of
+// the coordinate origin on every axis (E: the largest finite |c +- r| of the scene's spheres,
+// the extent the pad 1e-5 (1 + E) is built from): the quadratic cancels in |oc|^2 - r^2 and in
+// b^2 - 4a cc and reports hits up to 4 sqrt(2^-53) |oc| outside the sphere.  A ray from
+// farther away (NaN included) is not culled at all: the trees test every box as hit
+// (make_raybox), the light grids every sphere (occluded_lgrid), and a camera out there gets
+// no view grid (rt_scene_upload).  The test runs on the f32 images of the coordinates (the
+// slab tests round the origin to f32 anyway) against the reach rounded down to f32.
+// constexpr: the host builders, their mirrors and the kernels share these functions.
+constexpr double kCullReach = 32.0;
+constexpr float cull_reach(double extent) {
+    const double r = kCullReach * (1.0 + extent);
+    const float f = static_cast<float>(r < 3.0e38 ? r : 3.0e38);
+    return static_cast<double>(f) > r ? f * (1.0f - 0x1p-23f) : f;      // never above r
+}
+constexpr bool beyond_reach(float x, float y, float z, float reach) {
+    return !((x < 0.0f ? -x : x) <= reach && (y < 0.0f ? -y : y) <= reach && (z < 0.0f ? -z : z) <= reach);
+}
+constexpr bool beyond_reach(const double p[3], float reach) {
+    return beyond_reach(static_cast<float>(p[0]), static_cast<float>(p[1]), static_cast<float>(p[2]), reach);
+}
+
 struct DevScene {
     const DevSphere* spheres;       // file order among spheres (or BVH order, see sphere_obj)
     const int32_t* sphere_obj;      // object id of each sphere (tie-break key, material index)
@@ -172,6 +195,7 @@ struct DevScene {
     const DevQNode4* q4;             // the quantised 4-wide tree (null: not representable)
     int32_t n_q4;                    // its nodes (breadth-first; root = node 0)
     int32_t pfxq;                    // nodes [0, pfxq) staged in LDS by the quantised-tree source (set per render)
+    float cull_reach;                // rays starting beyond it on some axis are not culled (above)
 };
 
 struct FrameParams {

@@ -3,6 +3,7 @@
 #include <new>
 #include <string>
 
+#include "device_layout.hpp"
 #include "host_scene.hpp"
 
 extern "C" {
@@ -71,6 +72,8 @@ int rt_scene_get_desc(const rt_scene* s, rt_scene_desc* out) {
 void rt_scene_free(rt_scene* s) { delete s; }
 
 int rt_abi_version(void) { return RT_ABI_VERSION; }
+
+double rt_cull_reach(double extent) { return rtamd::cull_reach(extent); }
 
 void rt_render_opts_default(rt_render_opts* o, uint32_t width, uint32_t height) {
     if (!o) return;

@@ -271,8 +271,9 @@ LightGridResult build_view_grid(const std::vector<DevSphere>& spheres, const std
 // The device's candidate list for a shadow query from p toward light `li`
 // (occluded_lgrid, trace_common.hpp), with the same f32 arithmetic: the always
 // list, then p's cell up to the early stop.  Returns false when the device
-// would test every sphere (degenerate direction) or the light has no grid.
-bool light_grid_candidates(const LightGridResult& lg, int li, const double p[3], std::vector<int32_t>& out) {
+// would test every sphere (degenerate direction, or p beyond the culling domain
+// `reach`, DevScene::cull_reach) or the light has no grid.
+bool light_grid_candidates(const LightGridResult& lg, int li, const double p[3], float reach, std::vector<int32_t>& out) {
     out.clear();
     if (li < 0 || li >= static_cast<int>(lg.grids.size())) return false;
     const DevLightGrid& g = lg.grids[li];
@@ -285,7 +286,7 @@ bool light_grid_candidates(const LightGridResult& lg, int li, const double p[3],
     const float da = fa == 0 ? dx : fa == 1 ? dy : dz;
     const float db = fa == 0 ? dy : fa == 1 ? dz : dx;
     const float dc = fa == 0 ? dz : fa == 1 ? dx : dy;
-    if (!(std::fabs(da) > 0.0f && std::fabs(da) < 3.0e38f)) return false;
+    if (!(std::fabs(da) > 0.0f && std::fabs(da) < 3.0e38f) || beyond_reach(p, reach)) return false;
     const int f = 2 * fa + (da < 0.0f ? 1 : 0);
     const float inv = 1.0f / std::fabs(da);
     const float R = static_cast<float>(g.R);

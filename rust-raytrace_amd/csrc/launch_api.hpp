@@ -124,6 +124,9 @@ hipError_t launch_path_warmup(hipStream_t s);
 hipError_t launch_div_a2_probe(const double* x, const double* a, uint32_t n, double* fast, double* slow, hipStream_t s);
 // Diagnostic: sqrt_win(x) and sqrt(x) on the device (rt_sqrt_check).
 hipError_t launch_sqrt_probe(const double* x, uint32_t n, double* fast, double* slow, hipStream_t s);
+// Diagnostic: the tree walks' f32 culling arithmetic on n (ray, box, t, code) records (rt_cull_check).
+hipError_t launch_cull_probe(uint32_t n, const double* rays, const float* boxes, const double* t, const int32_t* codes,
+                             float reach, int32_t* out_i, float* out_f, hipStream_t s);
 
 // The general path (path_kernel.hip): every material / light / camera class,
 // keyed random draws, one work-item per pixel over the HBM recursion stack.

@@ -115,6 +115,37 @@ int rt_div_a2_check(rt_ctx* c, const double* x, const double* a, uint32_t n, dou
     });
 }
 
+int rt_cull_check(rt_ctx* c, uint32_t n, const double* rays, const float* boxes, const double* t, const int32_t* codes,
+                  double reach, int32_t* out_i, float* out_f) {
+    if (!c || (n && (!rays || !boxes || !t || !codes || !out_i || !out_f))) return RT_E_INVALID;
+    if (n == 0) return RT_OK;
+    return guarded(c, [&] {
+        HIP_TRY(c, hipSetDevice(c->device));
+        // one allocation: [rays 48 n][t 8 n][boxes 24 n][codes 4 n][out_i 20 n][out_f 20 n]
+        const size_t N = n;
+        const size_t o_t = 48 * N, o_box = o_t + 8 * N, o_code = o_box + 24 * N, o_oi = o_code + 4 * N, o_of = o_oi + 20 * N;
+        uint8_t* d = nullptr;
+        HIP_TRY(c, hipMalloc(&d, o_of + 20 * N));
+        auto body = [&]() -> int {
+            HIP_TRY(c, hipMemcpyAsync(d, rays, 48 * N, hipMemcpyHostToDevice, c->stream));
+            HIP_TRY(c, hipMemcpyAsync(d + o_t, t, 8 * N, hipMemcpyHostToDevice, c->stream));
+            HIP_TRY(c, hipMemcpyAsync(d + o_box, boxes, 24 * N, hipMemcpyHostToDevice, c->stream));
+            HIP_TRY(c, hipMemcpyAsync(d + o_code, codes, 4 * N, hipMemcpyHostToDevice, c->stream));
+            HIP_TRY(c, launch_cull_probe(n, reinterpret_cast<const double*>(d), reinterpret_cast<const float*>(d + o_box),
+                                         reinterpret_cast<const double*>(d + o_t), reinterpret_cast<const int32_t*>(d + o_code),
+                                         static_cast<float>(reach), reinterpret_cast<int32_t*>(d + o_oi), reinterpret_cast<float*>(d + o_of),
+                                         c->stream));
+            HIP_TRY(c, hipMemcpyAsync(out_i, d + o_oi, 20 * N, hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(c, hipMemcpyAsync(out_f, d + o_of, 20 * N, hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(c, hipStreamSynchronize(c->stream));
+            return RT_OK;
+        };
+        const int rc = body();
+        (void)hipFree(d);
+        return rc;
+    });
+}
+
 int rt_sqrt_check(rt_ctx* c, const double* x, uint32_t n, double* fast, double* slow) {
     if (!c || (n && (!x || !fast || !slow))) return RT_E_INVALID;
     if (n == 0) return RT_OK;

@@ -64,7 +64,7 @@ int rt_light_grid_candidates(const rt_scene* s, int light, int resolution, const
         std::vector<int32_t> cand;
         size_t used = 0;
         for (uint32_t i = 0; i < n_points; ++i) {
-            if (!light_grid_candidates(lg, light, points + 3 * i, cand)) { counts[i] = -1; continue; }
+            if (!light_grid_candidates(lg, light, points + 3 * i, cull_reach(extent), cand)) { counts[i] = -1; continue; }
             counts[i] = static_cast<int32_t>(cand.size());
             for (int32_t k : cand) {
                 if (used == cap) return fail(nullptr, RT_E_INVALID, "candidate buffer too small");
@@ -109,8 +109,12 @@ int rt_view_grid_candidates(const rt_scene* s, int resolution, const double* dir
                 for (double v : {o.geom[k] - r, o.geom[k] + r})
                     if (std::isfinite(v)) extent = std::max(extent, std::fabs(v));
         }
-        const LightGridResult g = build_view_grid(spheres, srad, s->camera.position, 1e-5 * (1.0 + extent),
-                                                  view_grid_res(s, resolution), view_grid_cap(spheres.size()));
+        // as rt_scene_upload: no grid for a camera beyond the culling domain (every ray: -1)
+        const double* cpos = s->camera.position;
+        LightGridResult g;
+        if (beyond_reach(cpos, cull_reach(extent))) g.grids.push_back(DevLightGrid{});
+        else g = build_view_grid(spheres, srad, cpos, 1e-5 * (1.0 + extent), view_grid_res(s, resolution),
+                                 view_grid_cap(spheres.size()));
         const DevLightGrid& G = g.grids[0];
         if (info) {
             info[0] = G.R;
@@ -317,7 +321,12 @@ static int scene_upload(rt_ctx* c, const rt_scene* s) {
     // scene's own frame size, im_dist * max(W, H) / 8 cells per face side (tuning "cam_grid_res");
     // only for scenes the wavefront schedule can render (the path kernel never reads it)
     LightGridResult cg;
-    if (s->camera.kind == RT_CAMERA_SIMPLE && !needs_path && c->t(kTuneCamGridRes) >= 0)
+    // ... and whose camera lies inside the culling domain (device_layout.hpp): from farther away the
+    // padded boxes do not hold every hit the quadratic reports, and generation 0 walks the tree
+    const float reach = cull_reach(extent);
+    const double* cpos = s->camera.position;
+    if (s->camera.kind == RT_CAMERA_SIMPLE && !needs_path && c->t(kTuneCamGridRes) >= 0 &&
+        !beyond_reach(cpos, reach))
         cg = build_view_grid(spheres, r_leaf, s->camera.position, pad, view_grid_res(s, c->t(kTuneCamGridRes)),
                              view_grid_cap(spheres.size()));
     // One blob: [spheres][sphere_obj][planes][plane_obj][mats][lights][bvh], 256-B aligned pieces.
@@ -379,6 +388,7 @@ static int scene_upload(rt_ctx* c, const rt_scene* s) {
     auto* base = static_cast<uint8_t*>(c->d_blob);
     DevScene& d = c->dsc;
     d = DevScene{};
+    d.cull_reach = reach;
     d.spheres = reinterpret_cast<const DevSphere*>(base + o_sph);
     d.sphere_obj = reinterpret_cast<const int32_t*>(base + o_sobj);
     d.planes = reinterpret_cast<const DevPlane*>(base + o_pl);

@@ -397,15 +397,25 @@ __device__ __forceinline__ float inv_dir(double d) {
 #ifndef RT_DIR_SCALE
 #define RT_DIR_SCALE 1      // (A/B builds only: 0 = the round-4 unscaled slab tests, not exact for such rays)
 #endif
-__device__ __forceinline__ RayBox make_raybox(const Ray& r) {
+// reach: DevScene::cull_reach.  A ray that starts beyond it (device_layout.hpp, DESIGN.md §4 "the
+// far-origin rule") gets the null image, 1/d = 0: every slab bound is fma(v, 0, -0) = 0, so every box
+// test passes with entry t = 0 <= any t limit and the walk tests every sphere, as the linear scan does.
+// Decided once per ray; the slab tests themselves are the same for every ray.
+__device__ __forceinline__ RayBox make_raybox(const Ray& r, float reach) {
+    const float ox = static_cast<float>(r.ox), oy = static_cast<float>(r.oy), oz = static_cast<float>(r.oz);
+    const bool far = beyond_reach(ox, oy, oz, reach);
     const double m = fmax(fmax(fabs(r.dx), fabs(r.dy)), fabs(r.dz));
     // m = f 2^te with f in [0.5, 1) (v_frexp_exp_i32_f64); NaN and infinite directions keep
     // te = 0 (their t values are NaN anyway)
     const int32_t te = RT_DIR_SCALE && ((m > 0x1p20 && m < __builtin_huge_val()) || (m < 0x1p-20 && m > 0.0))
                            ? __builtin_amdgcn_frexp_exp(m) : 0;
-    const float ix = inv_dir(ldexp(r.dx, -te)), iy = inv_dir(ldexp(r.dy, -te)), iz = inv_dir(ldexp(r.dz, -te));
-    return RayBox{ix, iy, iz, -(static_cast<float>(r.ox) * ix), -(static_cast<float>(r.oy) * iy),
-                  -(static_cast<float>(r.oz) * iz), te};
+    // (-o/d follows as -(o * 0) = 0 for an origin within the f32 range.  Beyond it, or NaN, the f32
+    // image is not finite and the bounds of that axis are NaN: a NaN origin's sphere tests report
+    // nothing, a finite f64 origin beyond 3.4e38 is outside what the slab tests support.  Selecting
+    // -o/d as well measured 0.6% slower at C3)
+    const float ix = far ? 0.0f : inv_dir(ldexp(r.dx, -te)), iy = far ? 0.0f : inv_dir(ldexp(r.dy, -te)),
+                iz = far ? 0.0f : inv_dir(ldexp(r.dz, -te));
+    return RayBox{ix, iy, iz, -(ox * ix), -(oy * iy), -(oz * iz), te};
 }
 
 // Slab bound t at coordinate v along the axis with (1/d, -o/d) = (i, no).
@@ -439,6 +449,32 @@ __device__ __forceinline__ bool box_hit(const float* lo, const float* hi, const 
 #endif
     if (RT_BOXFOLD) return fmaxf(tn, 0.0f) <= fminf(tf, tlim);
     return tn <= tf && tf >= 0.0f && tn <= tlim;
+}
+
+// box_hit as the whole-LDS walk (nearest_bvh_bl, kNodes 2) runs it, on the box's NEAR bounds
+// (lo on an axis with 1/d >= 0, near_is_lo, else hi) and FAR bounds: fma(v, 1/d, -o/d) is
+// monotone in v for a fixed ray, so fma(near) = min(fma(lo), fma(hi)) exactly: box_hit's
+// interval, without its six min/max.  rt_cull_check probes this function beside box_hit.
+__device__ __forceinline__ bool near_is_lo(float inv) { return inv >= 0.0f; }
+__device__ __forceinline__ bool box_hit_nf(float nx, float ny, float nz, float fx, float fy, float fz, const RayBox& rb,
+                                           float tlim, float& tnear) {
+    const float a = fmaxf(fmaxf(slab_t(nx, rb.ix, rb.nox), slab_t(ny, rb.iy, rb.noy)), slab_t(nz, rb.iz, rb.noz));
+    const float b = fminf(fminf(slab_t(fx, rb.ix, rb.nox), slab_t(fy, rb.iy, rb.noy)), slab_t(fz, rb.iz, rb.noz));
+#if RT_WIDEN_MUL
+    // the relative widening as one multiply per bound (§4 item 2): t (1 - tol) for the
+    // entry, f (1 + tol) for the exit.  Where the two forms differ (t or f < 0) the
+    // compare below clamps t to 0 and a negative exit fails either way; +inf stays +inf
+    tnear = a * kWidenLo;
+    const float f = b * kWidenHi;
+#else
+    tnear = widen_lo(a);
+    const float f = widen_hi(b);
+#endif
+    // box_hit's folded test max(t, 0) <= min(f, tlim) as two compares: tlim is never
+    // NaN, and !(x > f) holds for a NaN f as min(f, tlim) = tlim does (no
+    // canonicalisation of tlim per visit, no min)
+    const float x = fmaxf(tnear, 0.0f);
+    return x <= tlim && !(x > f);
 }
 
 // An f32 bound >= t (t >= 0 or +inf), for culling boxes that start beyond t.
@@ -656,7 +692,7 @@ __device__ __forceinline__ Hit nearest_bvh(const DevScene& sc, const BvhView& v,
     if (h.nan_t || sc.n_spheres == 0) return h;
     const double a = r.dx * r.dx + r.dy * r.dy + r.dz * r.dz;
     const SphK sk = sphere_k(a);
-    const RayBox rb = make_raybox(r);
+    const RayBox rb = make_raybox(r, sc.cull_reach);
     float tlim = h.obj == INT32_MAX ? __builtin_inff() : t_limit(rb, h.t);
     RT_STACK_DECL(kReg, uint64_t);
     int32_t cur = sc.bvh_root;
@@ -710,7 +746,7 @@ __device__ __forceinline__ Hit nearest_bvh_bl(const DevScene& sc, const BvhView&
     if (h.nan_t || sc.n_spheres == 0) return h;
     const double a = r.dx * r.dx + r.dy * r.dy + r.dz * r.dz;
     const SphK sk = sphere_k(a);
-    const RayBox rb = make_raybox(r);
+    const RayBox rb = make_raybox(r, sc.cull_reach);
     float tlim = h.obj == INT32_MAX ? __builtin_inff() : t_limit(rb, h.t);
     // not a node and no leaf code: INT32_MIN (~cur would list 8 spheres at 2^28), or 0 for the
     // byte-offset nodes of the whole-LDS walk (node c is (c + 1) * 8)
@@ -744,9 +780,9 @@ __device__ __forceinline__ Hit nearest_bvh_bl(const DevScene& sc, const BvhView&
     if constexpr (kNodes == 2) {
         const char* L = reinterpret_cast<const char*>(v.lnodes) - 8;
         const size_t n8 = static_cast<size_t>(v.nl) * 8;
-        nxa = L + (rb.ix >= 0.0f ? 0 : n8); fxa = L + (rb.ix >= 0.0f ? n8 : 0);
-        nya = L + 2 * n8 + (rb.iy >= 0.0f ? 0 : n8); fya = L + 2 * n8 + (rb.iy >= 0.0f ? n8 : 0);
-        nza = L + 4 * n8 + (rb.iz >= 0.0f ? 0 : n8); fza = L + 4 * n8 + (rb.iz >= 0.0f ? n8 : 0);
+        nxa = L + (near_is_lo(rb.ix) ? 0 : n8); fxa = L + (near_is_lo(rb.ix) ? n8 : 0);
+        nya = L + 2 * n8 + (near_is_lo(rb.iy) ? 0 : n8); fya = L + 2 * n8 + (near_is_lo(rb.iy) ? n8 : 0);
+        nza = L + 4 * n8 + (near_is_lo(rb.iz) ? 0 : n8); fza = L + 4 * n8 + (near_is_lo(rb.iz) ? n8 : 0);
         ca = L + 6 * n8;
     }
     for (;;) {
@@ -760,26 +796,8 @@ __device__ __forceinline__ Hit nearest_bvh_bl(const DevScene& sc, const BvhView&
                 auto pair = [cur](const char* base) { return *reinterpret_cast<const float2*>(base + cur); };
                 const float2 nx = pair(nxa), fx = pair(fxa), ny = pair(nya), fy = pair(fya), nz = pair(nza), fz = pair(fza);
                 const int2 cc = *reinterpret_cast<const int2*>(ca + cur);
-                const float a0 = fmaxf(fmaxf(slab_t(nx.x, rb.ix, rb.nox), slab_t(ny.x, rb.iy, rb.noy)), slab_t(nz.x, rb.iz, rb.noz));
-                const float a1 = fmaxf(fmaxf(slab_t(nx.y, rb.ix, rb.nox), slab_t(ny.y, rb.iy, rb.noy)), slab_t(nz.y, rb.iz, rb.noz));
-                const float b0 = fminf(fminf(slab_t(fx.x, rb.ix, rb.nox), slab_t(fy.x, rb.iy, rb.noy)), slab_t(fz.x, rb.iz, rb.noz));
-                const float b1 = fminf(fminf(slab_t(fx.y, rb.ix, rb.nox), slab_t(fy.y, rb.iy, rb.noy)), slab_t(fz.y, rb.iz, rb.noz));
-#if RT_WIDEN_MUL
-                // the relative widening as one multiply per bound (§4 item 2): t (1 - tol) for the
-                // entry, f (1 + tol) for the exit.  Where the two forms differ (t or f < 0) the
-                // compare below clamps t to 0 and a negative exit fails either way; +inf stays +inf
-                t0 = a0 * kWidenLo; t1 = a1 * kWidenLo;
-                const float f0 = b0 * kWidenHi, f1 = b1 * kWidenHi;
-#else
-                t0 = widen_lo(a0); t1 = widen_lo(a1);
-                const float f0 = widen_hi(b0), f1 = widen_hi(b1);
-#endif
-                // box_hit's folded test max(t, 0) <= min(f, tlim) as two compares: tlim is never
-                // NaN, and !(x > f) holds for a NaN f as min(f, tlim) = tlim does (no
-                // canonicalisation of tlim per visit, no min)
-                const float x0 = fmaxf(t0, 0.0f), x1 = fmaxf(t1, 0.0f);
-                h0 = x0 <= tlim && !(x0 > f0);
-                h1 = x1 <= tlim && !(x1 > f1);
+                h0 = box_hit_nf(nx.x, ny.x, nz.x, fx.x, fy.x, fz.x, rb, tlim, t0);
+                h1 = box_hit_nf(nx.y, ny.y, nz.y, fx.y, fy.y, fz.y, rb, tlim, t1);
                 c0 = cc.x;
                 c1 = cc.y;
             } else {
@@ -846,7 +864,7 @@ __device__ __forceinline__ bool occluded_bvh(const DevScene& sc, const BvhView& 
         double t;
         if (sphere_t(v.sph[hint], r, sk, t) && (!has_range || t * t < r2)) return true;
     }
-    const RayBox rb = make_raybox(r);
+    const RayBox rb = make_raybox(r, sc.cull_reach);
     // t*t < r2 implies t < sqrt(r2) (up to rounding, covered by t_limit's margin)
     const float tlim = has_range ? t_limit(rb, sqrt(r2)) : __builtin_inff();
     RT_STACK_DECL(kReg, int32_t);
@@ -958,7 +976,7 @@ __device__ __forceinline__ Hit nearest_q4(const DevScene& sc, const BvhView& v, 
     if (h.nan_t || sc.n_spheres == 0) return h;
     const double a = r.dx * r.dx + r.dy * r.dy + r.dz * r.dz;
     const SphK sk = sphere_k(a);
-    const RayBox rb = make_raybox(r);
+    const RayBox rb = make_raybox(r, sc.cull_reach);
     float tlim = h.obj == INT32_MAX ? __builtin_inff() : t_limit(rb, h.t);
     const bool fx = rb.ix < 0.0f, fy = rb.iy < 0.0f, fz = rb.iz < 0.0f;     // near slab bound = hi
     RT_STACK_DECL_N(0, uint64_t, kQ4Stack);
@@ -1058,7 +1076,7 @@ __device__ __forceinline__ bool occluded_bvh4(const DevScene& sc, const BvhView&
         double t;
         if (sphere_t(v.sph[hint], r, sk, t) && (!has_range || t * t < r2)) return true;
     }
-    const RayBox rb = make_raybox(r);
+    const RayBox rb = make_raybox(r, sc.cull_reach);
     const float tlim = has_range ? t_limit(rb, sqrt(r2)) : __builtin_inff();
     // pushes are unconditional stores at the stack top (junk when nothing is
     // pushed; the next push overwrites it): no branch per child
@@ -1130,7 +1148,8 @@ __device__ __forceinline__ bool occluded_lgrid(const DevScene& sc, const BvhView
     const float da = fa == 0 ? dx : fa == 1 ? dy : dz;
     const float db = fa == 0 ? dy : fa == 1 ? dz : dx;
     const float dc = fa == 0 ? dz : fa == 1 ? dx : dy;
-    if (!(fabsf(da) > 0.0f && fabsf(da) < 3.0e38f)) {
+    // ... and so does a shade point beyond the culling domain (the far-origin rule)
+    if (!(fabsf(da) > 0.0f && fabsf(da) < 3.0e38f) || beyond_reach(static_cast<float>(ptx), static_cast<float>(pty), static_cast<float>(ptz), sc.cull_reach)) {
         for (int32_t k = 0; k < sc.n_spheres; ++k)
             if (blocks(k)) return true;
         return false;

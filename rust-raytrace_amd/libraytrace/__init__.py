@@ -20,7 +20,7 @@ PKG_DIR = os.path.dirname(_HERE)
 LIB_PATH = os.environ.get("RT_LIBRTAMD") or os.path.join(PKG_DIR, "librtamd.so")
 HEADER_PATH = os.path.join(os.path.dirname(PKG_DIR), "include", "raytrace_amd.h")
 
-RT_ABI_VERSION = 7               # include/raytrace_amd.h
+RT_ABI_VERSION = 8               # include/raytrace_amd.h
 RT_OK = 0
 RT_E_INVALID, RT_E_NODEVICE, RT_E_HIP, RT_E_NOMEM = -1, -2, -3, -4
 RT_E_UNSUPPORTED, RT_E_PARSE, RT_E_NOSCENE, RT_E_IO = -5, -6, -7, -8
@@ -143,6 +143,9 @@ def _load():
         "rt_div_a2_check": (C.c_int, [C.c_void_p, P(C.c_double), P(C.c_double), C.c_uint32, P(C.c_double),
                                       P(C.c_double)]),
         "rt_sqrt_check": (C.c_int, [C.c_void_p, P(C.c_double), C.c_uint32, P(C.c_double), P(C.c_double)]),
+        "rt_cull_check": (C.c_int, [C.c_void_p, C.c_uint32, P(C.c_double), P(C.c_float), P(C.c_double), P(C.c_int32),
+                                    C.c_double, P(C.c_int32), P(C.c_float)]),
+        "rt_cull_reach": (C.c_double, [C.c_double]),
         "rt_ctx_set_tuning": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int64]),
         "rt_ctx_get_tuning": (C.c_int, [C.c_void_p, C.c_char_p, P(C.c_int64)]),
         "rt_tuning_key": (C.c_char_p, [C.c_int]),
@@ -336,6 +339,11 @@ class Scene:
             pass
 
 
+def cull_reach(extent):
+    """rt_cull_reach: the culling domain of a scene whose spheres' largest |centre +- radius| is extent."""
+    return lib.rt_cull_reach(float(extent))
+
+
 def device_count():
     n = C.c_int(0)
     lib.rt_device_count(C.byref(n))
@@ -492,6 +500,27 @@ class Context:
         _check(lib.rt_sqrt_check(self._h, x.ctypes.data_as(P), x.size, fast.ctypes.data_as(P), slow.ctypes.data_as(P)),
                self._h)
         return fast, slow
+
+    def cull_check(self, rays, boxes, t, codes, reach=float("inf")):
+        """Diagnostic (rt_cull_check): the tree walks' f32 culling arithmetic on n records: rays [n, 6]
+        float64 (origin, direction), boxes [n, 6] float32 (lo, hi), t [n] float64 (+inf: no limit), codes
+        [n] int32, reach the culling domain (cull_reach(extent); inf: every origin inside).  Returns a dict
+        of [n] arrays: te, tlim, hit, tnear (box_hit), hit_nf, tnear_nf (the whole-LDS walk's near / far
+        form), node16, t16, node18, t18 (the compact stack entries of (code, tnear) read back)."""
+        rays = np.ascontiguousarray(rays, dtype=np.float64)
+        boxes = np.ascontiguousarray(boxes, dtype=np.float32)
+        t = np.ascontiguousarray(t, dtype=np.float64)
+        codes = np.ascontiguousarray(codes, dtype=np.int32)
+        n = t.size
+        assert rays.shape == (n, 6) and boxes.shape == (n, 6) and t.shape == (n,) and codes.shape == (n,)
+        oi = np.empty((n, 5), np.int32)
+        of = np.empty((n, 5), np.float32)
+        PD, PF, PI = C.POINTER(C.c_double), C.POINTER(C.c_float), C.POINTER(C.c_int32)
+        _check(lib.rt_cull_check(self._h, n, rays.ctypes.data_as(PD), boxes.ctypes.data_as(PF), t.ctypes.data_as(PD),
+                                 codes.ctypes.data_as(PI), float(reach), oi.ctypes.data_as(PI), of.ctypes.data_as(PF)),
+               self._h)
+        return {"te": oi[:, 0], "hit": oi[:, 1] != 0, "hit_nf": oi[:, 2] != 0, "node16": oi[:, 3], "node18": oi[:, 4],
+                "tlim": of[:, 0], "tnear": of[:, 1], "tnear_nf": of[:, 2], "t16": of[:, 3], "t18": of[:, 4]}
 
     def accumulator(self, opts):
         """rt_accum_create: a progressive render of opts' tile (main.rs:47-56 split over calls), bound to

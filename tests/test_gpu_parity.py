@@ -17,6 +17,7 @@ from libraytrace import scenes
 from oracle import ref64
 from adversarial_scenes import (tiny as _tiny, nan_plane_scene as _nan_plane_scene, axis_tie_scene as _axis_tie_scene,
                                 coincident_scene, extreme_magnitudes_scene)
+import far_scenes
 
 pytestmark = pytest.mark.gpu
 
@@ -346,6 +347,37 @@ def test_extreme_sphere_sizes_and_far_plane_origins(gpu_ctx, algo):
     s.sphere((0.0, -1e4 + 0.0, -5.0), 1e4, scenes.phong((0.2, 0.2, 0.2), (0.5, 0.5, 0.5), 5.0, (0, 0, 0)))
     s.sphere((1e5, 3.0, -1e5), 2e3, scenes.phong((0.9, 0.9, 0.2), (0.2, 0.2, 0.2), 5.0, (0, 0, 0)))
     check_parity(gpu_ctx, s, algo)
+
+
+# Far ray origins ("the far-origin rule"; far_scenes.py): the f64 quadratic reports
+# hits far outside a small sphere's padded box once the ray starts far away, and the linear scan
+# (the oracle) takes them.  name -> (algorithm, tuning, spheres): the tree walk with compact and
+# with 64-bit stack entries, the linear scan, the path kernel, the quantised tree, the binary tree
+# alone (no view grid, no light grids: camera and shadow rays walk trees) and, with enough spheres
+# for a tree beyond LDS, the binary16 nodes.
+FAR_SCHEDULES = {
+    "wavefront": (lr.RT_ALGO_WAVEFRONT, {}, 40),
+    "brute": (lr.RT_ALGO_WAVEFRONT_BRUTE, {}, 40),
+    "path": (lr.RT_ALGO_PATH, {}, 40),
+    "wide_stack": (lr.RT_ALGO_WAVEFRONT, dict(compact_stack=0), 40),
+    "qtree": (lr.RT_ALGO_WAVEFRONT, dict(src=25, src_occ=11), 40),
+    "tree_alone": (lr.RT_ALGO_WAVEFRONT, dict(cam_grid_res=-1, light_grids=0), 40),
+    "half_nodes": (lr.RT_ALGO_WAVEFRONT, dict(half_nodes=1), 1500),
+}
+FAR_FRAMES = {"telephoto_1e4": lambda n: far_scenes.telephoto(1e4, n), "telephoto_1e5": lambda n: far_scenes.telephoto(1e5, n),
+              "floor_1e6": lambda n: far_scenes.floor(1e6, n)}
+
+
+@pytest.mark.parametrize("schedule", list(FAR_SCHEDULES))
+@pytest.mark.parametrize("frame", list(FAR_FRAMES))
+def test_far_ray_origins_match_oracle(gpu_ctx, frame, schedule):
+    """A camera 1e4 and 1e5 away from 40 spheres of radius 1e-5..1e-4 (every camera ray starts far
+    away), and a floor 1e6 away from such spheres in front of a point light (every shadow ray
+    does): bytes, colours, rays and shadow rays of every schedule equal the oracle's.  Before the
+    far-origin rule the culling schedules dropped reported hits here."""
+    algo, tuning, n = FAR_SCHEDULES[schedule]
+    with _with_tuning(gpu_ctx, **tuning):
+        check_parity(gpu_ctx, FAR_FRAMES[frame](n), algo)
 
 
 def _sphere_chain_scene():
