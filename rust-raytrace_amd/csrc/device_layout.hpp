@@ -287,11 +287,13 @@ struct PathStack {
 //            array per generation (generation k at k*qcap), so the nearest-hit
 //            kernels never wait for the shadow / shading kernels of earlier
 //            generations (the other stream);
-//   levels   per-level local colour r,g,b and Schlick factor (f64)
-//            [4][levels*capa], then object id (i32) [levels*capa]; [k*capa + c]
-//            for chain c (chain = the entry of the lit camera hit's generation-0
-//            record, capa >= qcap; its pixel is cpix[c]), so a generation's
-//            levels are written in about its records' order;
+//   levels   one packed entry per level (WfLevel, 32 B: local colour r,g,b and
+//            the fold's Schlick factor, f64) [levels*capa], then object id (i32)
+//            [levels*capa]; [k*capa + c] for chain c (chain = the entry of the lit
+//            camera hit's generation-0 record, capa >= qcap; its pixel is cpix[c]),
+//            so a generation's levels are written in about its records' order;
+//            a level is one whole 32-B sector plus 4 B whatever became of the
+//            chain's neighbours;
 //   term     terminal colour of each chain [3][capa] (f64), then nlev (u8,
 //            levels pushed) [capa];
 //   rq / rs  [k*G + r]: entries of region r of Q_k / of generation k's records;
@@ -306,6 +308,23 @@ struct PathStack {
 //            order and read by wf_compose, which writes the frame row by row.
 // Queue and record arrays are G regions of R entries (qcap = G*R); region r is
 // written only by workgroup r of the producing kernel.
+// One level of a chain: the local colour its shading left and the factor its
+// fold multiplies by beside the object's ks: the Schlick factor of a
+// FresnelMaterial hit, exactly 1.0 for any other (raytrace.rs:63 / 163).  One
+// aligned 32-B sector: written by one lane as two 16-B stores, read as two
+// 16-B loads.  (mem is 256-B aligned and o_lev a multiple of 256.)
+struct alignas(32) WfLevel {
+    double r, g, b, f;
+};
+static_assert(sizeof(WfLevel) == 32, "a level entry is one 32-B sector");
+// Which form a chunk's levels take is the schedule's choice (every kernel of the chunk is launched
+// for the same one): packed entries pay where levels are sparse, the word-per-array form (lf(0..3):
+// four f64 arrays over the same bytes, f written for FresnelMaterial hits only) where the fold
+// reads only the dense first levels.  A chunk whose fused tail starts at generation T <= 5 (a rank's
+// share of a frame) leaves its fold the levels 0 .. T-2: words.  No tail, or a late one: packed.
+// (DESIGN.md §9 has the measurements.)
+constexpr bool levels_packed(int tail_fuse) { return tail_fuse == 0 || tail_fuse >= 6; }
+
 struct WfBufs {
     unsigned char* mem;
     unsigned long long* totals;     // [0] nearest queries, [1] shadow queries, [2..3] nearest box / sphere
@@ -339,11 +358,11 @@ struct WfBufs {
     RT_HD uint32_t* ru(int f) const {             // 0 object, 1 primitive, 2 chain, 3 occlusion
         return reinterpret_cast<uint32_t*>(reinterpret_cast<double*>(mem + o_rec) + 7 * rn()) + f * rn();
     }
-    // levels (index = k * capa + chain): f = 0..2 colour, 3 Schlick factor
+    // levels (index = k * capa + chain): the packed colour entries, or, in the word-per-array form
+    // of the same bytes (levels_packed above), f = 0..2 colour, 3 Schlick factor; then the object ids
+    RT_HD WfLevel* lev() const { return reinterpret_cast<WfLevel*>(mem + o_lev); }
     RT_HD double* lf(int f) const { return reinterpret_cast<double*>(mem + o_lev) + static_cast<uint64_t>(f) * levels * capa; }
-    RT_HD int32_t* lobj() const {
-        return reinterpret_cast<int32_t*>(reinterpret_cast<double*>(mem + o_lev) + static_cast<uint64_t>(4) * levels * capa);
-    }
+    RT_HD int32_t* lobj() const { return reinterpret_cast<int32_t*>(lev() + static_cast<uint64_t>(levels) * capa); }
     RT_HD double* term(int f) const { return reinterpret_cast<double*>(mem + o_term) + static_cast<uint64_t>(f) * capa; }
     RT_HD uint8_t* nlev() const { return reinterpret_cast<uint8_t*>(reinterpret_cast<double*>(mem + o_term) + 3ull * capa); }
     RT_HD uint32_t* cpix() const { return reinterpret_cast<uint32_t*>(mem + o_cpix); }   // chain -> chunk pixel

@@ -592,6 +592,28 @@ __device__ __forceinline__ void emit_chain(const FrameParams& fp, const WfBufs& 
     }
 }
 
+// A level entry (WfLevel at index at = k * capa + chain) moves as its two 16-B halves {r, g} and
+// {b, f}: one lane writes, and later reads, one whole aligned 32-B sector.  f: the factor the fold
+// multiplies by beside ks (the Schlick factor of a FresnelMaterial hit, else exactly 1.0).
+typedef double F64x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ void store_level(const WfBufs& b, size_t at, Col res, double f) {
+    F64x2* e = reinterpret_cast<F64x2*>(b.lev() + at);
+    stn(e, F64x2{res.r, res.g});
+    stn(e + 1, F64x2{res.b, f});
+}
+// kF false (a scene without FresnelMaterial: every f is 1.0): f is not fetched, 24 B of the sector.
+template <bool kF>
+__device__ __forceinline__ WfLevel load_level(const WfBufs& b, size_t at) {
+    const F64x2* e = reinterpret_cast<const F64x2*>(b.lev() + at);
+    const F64x2 lo = ldn_if<kNtFold>(e);
+    if constexpr (kF) {
+        const F64x2 hi = ldn_if<kNtFold>(e + 1);
+        return WfLevel{lo[0], lo[1], hi[0], hi[1]};
+    } else {
+        return WfLevel{lo[0], lo[1], ldn_if<kNtFold>(&b.lev()[at].b), 1.0};
+    }
+}
+
 // Chain c ends in generation k with colour col (wf_fold folds its k levels onto it).
 __device__ __forceinline__ void set_terminal(const WfBufs& b, uint32_t c, Col col, int k) {
     stn(&b.term(0)[c], col.r); stn(&b.term(1)[c], col.g); stn(&b.term(2)[c], col.b);
@@ -867,7 +889,7 @@ struct ShadeOut {
 // wf_nearest); any other hit ends the chain with it.  kTerm = false (the fused
 // tail): a non-specular hit's colour is returned for the caller's in-register
 // fold instead of being written as the chain's terminal.
-template <bool kFresnel, bool kTerm = true>
+template <bool kFresnel, bool kTerm = true, bool kPack = false>
 __device__ __forceinline__ ShadeOut shade_compute(const DevScene& sc, const WfBufs& b, int k, const ShadeIn& in) {
     const double ptx = in.ptx, pty = in.pty, ptz = in.ptz, dx = in.dx, dy = in.dy, dz = in.dz, sig = in.sig;
     const int32_t obj = in.obj;
@@ -889,9 +911,14 @@ __device__ __forceinline__ ShadeOut shade_compute(const DevScene& sc, const WfBu
     }
     if (specular) {
         const size_t st = static_cast<size_t>(k) * b.capa + c;
-        stn(&b.lf(0)[st], res.r); stn(&b.lf(1)[st], res.g); stn(&b.lf(2)[st], res.b);
-        stn(&b.lobj()[st], obj);
-        if (kFresnel && m.kind == kMatFresnel) stn(&b.lf(3)[st], sh.f);
+        if constexpr (kPack) {
+            store_level(b, st, res, kFresnel && m.kind == kMatFresnel ? sh.f : 1.0);
+            stn(&b.lobj()[st], obj);
+        } else {
+            stn(&b.lf(0)[st], res.r); stn(&b.lf(1)[st], res.g); stn(&b.lf(2)[st], res.b);
+            stn(&b.lobj()[st], obj);
+            if (kFresnel && m.kind == kMatFresnel) stn(&b.lf(3)[st], sh.f);
+        }
     } else if (kTerm) {
         set_terminal(b, c, res, k);
     }
@@ -965,7 +992,7 @@ __global__ __launch_bounds__(kWfThreads, Src<kSrc>::waves) void wf_occlusion(Dev
 }
 
 // The Phong sum of every shade record of generation k.
-template <bool kFresnel>
+template <bool kFresnel, bool kPack = false>
 __global__ __launch_bounds__(kWfThreads, RT_SHADE_WAVES) void wf_shade(DevScene sc, FrameParams fp, WfBufs b, int k) {
     __shared__ uint32_t s_scan[kMaxRegions + 1];
     __shared__ uint32_t s_wave[kWfThreads / 64];
@@ -988,7 +1015,7 @@ __global__ __launch_bounds__(kWfThreads, RT_SHADE_WAVES) void wf_shade(DevScene 
         ShadeIn nxt{};
         const bool have_n = jn < n;
         if (have_n) nxt = shade_load(b, rk + region_entry(s_scan, b.G, b.R, static_cast<uint32_t>(jn)), lit);
-        if (have) shade_compute<kFresnel>(sc, b, k, cur);
+        if (have) shade_compute<kFresnel, true, kPack>(sc, b, k, cur);
         cur = nxt;
         have = have_n;
     }
@@ -1018,14 +1045,14 @@ __device__ __forceinline__ uint32_t grid_shadow_mask(const DevScene& sc, const B
 // terminal colour and sets nlev (the generation it ended in) instead of writing
 // them: the caller folds the chain right away.  cnt[0][k] / cnt[1][k]: this
 // workgroup's shade records of generation k / rays queued for generation k.
-template <bool kFresnel, bool kCount, bool kSky>
+template <bool kFresnel, bool kCount, bool kSky, bool kPack>
 __device__ __forceinline__ Col tail_chain(const DevScene& sc, const FrameParams& fp, const WfBufs& b, const BvhView& v,
                                           int k, ShadeIn in, int& nlev, uint32_t (*cnt)[kMaxGenerations], Work& wn,
                                           Work& wsh) {
     const int k0 = k;
     for (;;) {
         in.mask = grid_shadow_mask<kCount>(sc, v, in.ptx, in.pty, in.ptz, in.prim, wsh);
-        const ShadeOut so = shade_compute<kFresnel, false>(sc, b, k, in);        // level k if specular
+        const ShadeOut so = shade_compute<kFresnel, false, kPack>(sc, b, k, in);        // level k if specular
         if (!so.specular) { nlev = k; return so.res; }
         const Ray r = reflect_ray(Ray{in.ptx, in.pty, in.ptz, in.dx, in.dy, in.dz}, in.ptx, in.pty, in.ptz, so.nx, so.ny,
                                   so.nz);                                   // raytrace.rs:58-64
@@ -1057,8 +1084,12 @@ __device__ __forceinline__ Col tail_chain(const DevScene& sc, const FrameParams&
 // recursion returns (acc = res_k + ks_k * acc); the loads of four levels are
 // issued together so a pixel costs about two memory round trips per four
 // levels instead of two per level.
+// The level's factor f comes with its colour (WfLevel: the writer stored 1.0 for
+// a hit that is not Fresnel), so the only dependent fetch is ks by the level's
+// object (an LDS copy of every object's ks measured within noise: DESIGN.md §9).
+// kPack false: the levels in the word-per-array form (levels_packed, device_layout.hpp).
 template <bool kFresnel>
-__device__ __forceinline__ Col fold_levels(const DevScene& sc, const WfBufs& b, uint32_t p, int nlev, Col acc) {
+__device__ __forceinline__ Col fold_level_words(const DevScene& sc, const WfBufs& b, uint32_t p, int nlev, Col acc) {
     constexpr int U = RT_FOLD_UNROLL;
     for (int k = nlev - 1; k >= 0; k -= U) {
         double sr[U], sg[U], sb[U];
@@ -1091,11 +1122,46 @@ __device__ __forceinline__ Col fold_levels(const DevScene& sc, const WfBufs& b, 
     }
     return acc;
 }
+template <bool kFresnel, bool kPack>
+__device__ __forceinline__ Col fold_levels(const DevScene& sc, const WfBufs& b, uint32_t p, int nlev, Col acc) {
+    if constexpr (!kPack) return fold_level_words<kFresnel>(sc, b, p, nlev, acc);
+    constexpr int U = RT_FOLD_UNROLL;
+    for (int k = nlev - 1; k >= 0; k -= U) {
+        WfLevel lv[U];
+        int32_t ob[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            if (k - u >= 0) {
+                const size_t at = static_cast<size_t>(k - u) * b.capa + p;
+                ob[u] = ldn_if<kNtFold>(&b.lobj()[at]);
+                lv[u] = load_level<kFresnel>(b, at);
+            }
+        }
+        double kr[U], kg[U], kb[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            if (k - u >= 0) {
+                const DevMaterial& m = sc.mats[ob[u]];
+                kr[u] = m.ks[0]; kg[u] = m.ks[1]; kb[u] = m.ks[2];
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            if (k - u >= 0) {                  // res + (ks * child) * f, f = 1 for Phong (raytrace.rs:63 / 163)
+                const double kf = kFresnel ? lv[u].f : 1.0;
+                acc.r = lv[u].r + (kr[u] * acc.r) * kf;
+                acc.g = lv[u].g + (kg[u] * acc.g) * kf;
+                acc.b = lv[u].b + (kb[u] * acc.b) * kf;
+            }
+        }
+    }
+    return acc;
+}
 
 template <bool kFresnel>
 __device__ __forceinline__ Col fold_pixel(const DevScene& sc, const WfBufs& b, uint32_t p, uint8_t nlev) {   // p: the chain
     const Col acc{ldn_if<kNtFold>(&b.term(0)[p]), ldn_if<kNtFold>(&b.term(1)[p]), ldn_if<kNtFold>(&b.term(2)[p])};
-    return fold_levels<kFresnel>(sc, b, p, nlev, acc);
+    return fold_levels<kFresnel, false>(sc, b, p, nlev, acc);
 }
 
 // The fused tail (WfStreams::tail_fuse = T): for a small chunk (one rank's
@@ -1118,7 +1184,7 @@ __device__ __forceinline__ Col fold_pixel(const DevScene& sc, const WfBufs& b, u
 // record loads and level stores stay coalesced.  gridDim.x workgroups, all
 // resident; workgroup w publishes its counts in region w and zeros in the
 // other regions r = w (mod gridDim.x) of every generation >= T.
-template <bool kFresnel, bool kCount, bool kAa = false, bool kSky = false>
+template <bool kFresnel, bool kCount, bool kAa = false, bool kSky = false, bool kPack = false>
 __global__ __launch_bounds__(kWfThreads, 4) void wf_tail(DevScene sc, FrameParams fp, WfBufs b, int T, int W) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     __shared__ uint32_t s_cnt[2][kMaxGenerations];
@@ -1142,8 +1208,8 @@ __global__ __launch_bounds__(kWfThreads, 4) void wf_tail(DevScene sc, FrameParam
         const size_t at = rk + region_entry(ql.scan, b.G, b.R, static_cast<uint32_t>(j));
         const ShadeIn in = shade_load(b, at, false);
         int nlev = 0;
-        const Col term = tail_chain<kFresnel, kCount, kSky>(sc, fp, b, v, T - 1, in, nlev, s_cnt, wn, wsh);
-        const Col folded = fold_levels<kFresnel>(sc, b, in.c, nlev, term);
+        const Col term = tail_chain<kFresnel, kCount, kSky, kPack>(sc, fp, b, v, T - 1, in, nlev, s_cnt, wn, wsh);
+        const Col folded = fold_levels<kFresnel, kPack>(sc, b, in.c, nlev, term);
         const Col res = kAa ? aa_sample(folded) : average_samples(folded, fp.spp);
         emit_chain<kAa>(fp, b, in.c, b.compose ? 0u : b.cpix()[in.c], res, s_srgb);
     }
@@ -1176,7 +1242,7 @@ __global__ __launch_bounds__(kWfThreads, 4) void wf_tail(DevScene sc, FrameParam
 // RT_FOLD_THREADS-thread workgroups (256: at the fold's ~96 VGPRs five of them,
 // 20 waves, fit a CU where one 1024-thread workgroup leaves 4 wave slots idle),
 // dealt block-major over (kWfThreads / RT_FOLD_THREADS) x G workgroups.
-template <bool kFresnel, bool kAa = false>
+template <bool kFresnel, bool kAa = false, bool kPack = false>
 __global__ __launch_bounds__(RT_FOLD_THREADS, RT_FOLD_WAVES) void wf_fold(DevScene sc, FrameParams fp, WfBufs b, uint32_t lo,
                                                                           uint32_t hi) {
     constexpr int kT = RT_FOLD_THREADS;
@@ -1209,7 +1275,7 @@ __global__ __launch_bounds__(RT_FOLD_THREADS, RT_FOLD_WAVES) void wf_fold(DevSce
     for (; static_cast<uint64_t>(rc) * 64u < n; rc += W) {
         const Head nxt = head(static_cast<uint64_t>(rc + W) * 64u + lane);
         if (cur.nlev >= lo && cur.nlev <= hi) {             // (kNlevRunning: not ended yet, or no chain)
-            const Col folded = fold_levels<kFresnel>(sc, b, cur.c, static_cast<int>(cur.nlev), cur.term);
+            const Col folded = fold_levels<kFresnel, kPack>(sc, b, cur.c, static_cast<int>(cur.nlev), cur.term);
             const Col res = kAa ? aa_sample(folded) : average_samples(folded, fp.spp);
             emit_chain<kAa>(fp, b, cur.c, cur.p, res, s_srgb);
         }
@@ -1272,7 +1338,7 @@ hipError_t launch_sky_pixels(const DevScene& sc, const FrameParams& fp, const Wf
 }
 
 hipError_t launch_fold(const DevScene& sc, const FrameParams& fp, const WfBufs& b, hipStream_t s, LaunchMarks* m,
-                       uint32_t lo, uint32_t hi) {
+                       uint32_t lo, uint32_t hi, bool packed) {
     hipError_t e;
     if (sc.skybox) {                           // the terminals of the chains that ended on a miss
         if (m && (e = m->begin(s)) != hipSuccess) return e;
@@ -1281,11 +1347,13 @@ hipError_t launch_fold(const DevScene& sc, const FrameParams& fp, const WfBufs& 
     }
     if (m && (e = m->begin(s)) != hipSuccess) return e;
     const dim3 grid(b.G * (kWfThreads / RT_FOLD_THREADS)), block(RT_FOLD_THREADS);
+#define RT_FOLD(FR, AA) do { if (packed) hipLaunchKernelGGL((wf_fold<FR, AA, true>), grid, block, 0, s, sc, fp, b, lo, hi); \
+                             else hipLaunchKernelGGL((wf_fold<FR, AA, false>), grid, block, 0, s, sc, fp, b, lo, hi); } while (0)
     if (fp.aa_acc) {                           // RT_ALGO_WAVEFRONT_AA: the sample's colour to the running sums
-        if (sc.has_fresnel) hipLaunchKernelGGL((wf_fold<true, true>), grid, block, 0, s, sc, fp, b, lo, hi);
-        else hipLaunchKernelGGL((wf_fold<false, true>), grid, block, 0, s, sc, fp, b, lo, hi);
-    } else if (sc.has_fresnel) hipLaunchKernelGGL((wf_fold<true>), grid, block, 0, s, sc, fp, b, lo, hi);
-    else hipLaunchKernelGGL((wf_fold<false>), grid, block, 0, s, sc, fp, b, lo, hi);
+        if (sc.has_fresnel) RT_FOLD(true, true); else RT_FOLD(false, true);
+    } else if (sc.has_fresnel) RT_FOLD(true, false);
+    else RT_FOLD(false, false);
+#undef RT_FOLD
     return m ? m->mark(s, kKfFold) : hipGetLastError();
 }
 
@@ -1661,8 +1729,11 @@ hipError_t launch_shading(const DevScene& sc, const FrameParams& fp, const WfBuf
         if (mb && (e = mb->mark(sb, kKfOcclusion)) != hipSuccess) return e;
     }
     if (mb && (e = mb->begin(sb)) != hipSuccess) return e;
-    if (sc.has_fresnel) hipLaunchKernelGGL(wf_shade<true>, grid, block, 0, sb, sc, fp, b, k);
-    else hipLaunchKernelGGL(wf_shade<false>, grid, block, 0, sb, sc, fp, b, k);
+    if (levels_packed(ws.tail_fuse)) {
+        if (sc.has_fresnel) hipLaunchKernelGGL((wf_shade<true, true>), grid, block, 0, sb, sc, fp, b, k);
+        else hipLaunchKernelGGL((wf_shade<false, true>), grid, block, 0, sb, sc, fp, b, k);
+    } else if (sc.has_fresnel) hipLaunchKernelGGL((wf_shade<true, false>), grid, block, 0, sb, sc, fp, b, k);
+    else hipLaunchKernelGGL((wf_shade<false, false>), grid, block, 0, sb, sc, fp, b, k);
     return mb ? mb->mark(sb, kKfShade) : hipSuccess;
 }
 
@@ -1679,18 +1750,20 @@ hipError_t launch_generation(const DevScene& sc, const FrameParams& fp, const Wf
             if ((e = hipEventRecord(ws.near_done[k], ws.a)) != hipSuccess) return e;
             if ((e = hipStreamWaitEvent(ws.b[0], ws.near_done[k], 0)) != hipSuccess) return e;
         }
-        if ((e = launch_fold(sc, fp, b, ws.b[0], ws.b[0] != ws.a ? ws.mb[0] : ws.ma, 0u, static_cast<uint32_t>(k - 1))) !=
-            hipSuccess)
+        if ((e = launch_fold(sc, fp, b, ws.b[0], ws.b[0] != ws.a ? ws.mb[0] : ws.ma, 0u, static_cast<uint32_t>(k - 1),
+                             levels_packed(ws.tail_fuse))) != hipSuccess)
             return e;
         if (ws.ma && (e = ws.ma->begin(ws.a)) != hipSuccess) return e;
         const size_t lds_t = staged_bytes<kSrcBvhL8C>(sc) + queue_lds_bytes(b.G);
-#define RT_TAIL_S(FR, AA, SKY) hipLaunchKernelGGL((wf_tail<FR, kCount, AA, SKY>), dim3(ws.tail_wgs), block, lds_t, ws.a, sc, fp, b, k, ws.tail_width)
+#define RT_TAIL_P(FR, AA, SKY, PK) hipLaunchKernelGGL((wf_tail<FR, kCount, AA, SKY, PK>), dim3(ws.tail_wgs), block, lds_t, ws.a, sc, fp, b, k, ws.tail_width)
+#define RT_TAIL_S(FR, AA, SKY) do { if (levels_packed(ws.tail_fuse)) RT_TAIL_P(FR, AA, SKY, true); else RT_TAIL_P(FR, AA, SKY, false); } while (0)
 #define RT_TAIL(FR, AA) do { if (sc.skybox) RT_TAIL_S(FR, AA, true); else RT_TAIL_S(FR, AA, false); } while (0)
         if (fp.aa_acc) { if (sc.has_fresnel) RT_TAIL(true, true); else RT_TAIL(false, true); }
         else if (sc.has_fresnel) RT_TAIL(true, false);
         else RT_TAIL(false, false);
 #undef RT_TAIL
 #undef RT_TAIL_S
+#undef RT_TAIL_P
         return ws.ma ? ws.ma->mark(ws.a, kKfTail) : hipGetLastError();
     }
     e = ws.ma ? ws.ma->begin(ws.a) : hipSuccess;
@@ -1787,7 +1860,9 @@ hipError_t launch_wavefront(const DevScene& sc, const FrameParams& fp, const WfB
     if ((e = join_b(ws, ws.tail_fuse > 0 ? 1u : (1u << ws.nb) - 1u)) != hipSuccess) return e;
     // the chains not folded yet (all of them without the fused tail, which folded every chain:
     // its own as it ended them, the others on a B stream)
-    if (ws.tail_fuse == 0 && (e = launch_fold(sc, fp, b, ws.a, ws.ma, 0u, kNlevRunning - 1u)) != hipSuccess) return e;
+    if (ws.tail_fuse == 0 &&
+        (e = launch_fold(sc, fp, b, ws.a, ws.ma, 0u, kNlevRunning - 1u, levels_packed(ws.tail_fuse))) != hipSuccess)
+        return e;
     const uint64_t segs = static_cast<uint64_t>((fp.tile_w + 63u) / 64u) * fp.rows;
     const dim3 row_grid(std::max(1u, static_cast<uint32_t>(std::min<uint64_t>(4u * b.G, (segs + kComposeWaves - 1) / kComposeWaves))));
     if (fp.aa_acc) {

@@ -6,7 +6,7 @@ Each input is the stderr of
           -Irust-raytrace_amd/csrc -c rust-raytrace_amd/csrc/trace_kernel.hip -o /dev/null \\
           -Rpass-analysis=kernel-resource-usage 2> LOG
 on one checkout (the same line on path_kernel.hip for the path kernel's pair).  Kernels are matched
-by demangled name (c++filt); a trailing `false` template argument of wf_nearest / wf_fold / wf_tail /
+by demangled name (c++filt); a trailing `false` template argument of wf_nearest / wf_fold / wf_tail / wf_shade /
 trace_frame_kernel / wf_compose / wf_aa_compose in the second build (a parameter the first build
 does not have; a kernel the first build has as a plain function loses its `<false>`) is dropped
 before matching.  Prints every kernel of the first build whose
@@ -45,7 +45,7 @@ def parse(path):
 
 
 def first_build_name(n):
-    m = re.match(r"(wf_nearest|wf_fold|wf_tail|trace_frame_kernel|wf_compose|wf_aa_compose)<(.*)>$", n)
+    m = re.match(r"(wf_nearest|wf_fold|wf_tail|wf_shade|trace_frame_kernel|wf_compose|wf_aa_compose)<(.*)>$", n)
     if not m:
         return n
     args = [a.strip() for a in m.group(2).split(",")]
