@@ -447,7 +447,7 @@ enum rt_kernel_family {
     RT_KF_TALLY = 4,        /* wf_tally */
     RT_KF_CAMERA = 5,       /* wf_nearest, generation 0 (camera rays) */
     RT_KF_COMPOSE = 6,      /* wf_compose: the row-ordered frame pass (tuning compose); RT_ALGO_WAVEFRONT_AA:
-                               wf_resolve after a chunk's last pass (and wf_aa_compose per pass, tuning compose);
+                               accum_resolve after a chunk's last pass (and wf_aa_compose per pass, tuning compose);
                                accum_resolve of an rt_accum_resolve after an RT_TIME_KERNELS rt_render_accumulate;
                                skybox scenes: wf_sky_pixels after the camera pass (compose 0) and wf_sky_term
                                before each fold */
@@ -460,7 +460,7 @@ int rt_ctx_kernel_times(rt_ctx* ctx, double* ms, uint32_t* launches, int n);
  * best).  Keys (rt_tuning_key(i) for i = 0, 1, ... until NULL):
  * chunk_pixels (wavefront chunk cap, 0: from the working-set budget), bvh_leaf, light_grids, light_grid_res
  * (these three take effect at the next rt_scene_upload), src, src_occ (the
- * nearest-hit and shadow sphere sources, trace_kernel.hip kSrc*; an unsupported
+ * nearest-hit and shadow sphere sources, wf_device.hpp kSrc*; an unsupported
  * pair falls back to the binary tree through L2), prefix_kb (KB of the tree's
  * top staged in LDS for trees beyond LDS), lanes, stagger_gen, regions, split,
  * bstreams, cam (generation 0: 3 the camera's view grid, -1 where built, other

@@ -221,7 +221,7 @@ struct FrameParams {
     // render (aa_pass 0: the camera rays are sample 0's).  A pass runs with spp = 1 (its tally counts
     // the pass's own rays) and finishes a pixel by adding the pass's sample colour to aa_acc.
     uint32_t aa_pass;               // the AA sample this pass traces (camera_ray's jitter key)
-    uint32_t aa_spp;                // the render's samples per pixel (wf_resolve divides by it)
+    uint32_t aa_spp;                // the render's samples per pixel (accum_resolve divides by it)
     uint32_t aa_flags;              // kAaTallyGens
     double* aa_acc;                 // per chunk pixel p: the f64 running sum r, g, b at [3p, 3p + 3) (a lane's
                                     //   working set, WfLayout::o_acc); pass 0 stores 0.0 + s_0, pass a adds s_a

@@ -1,4 +1,6 @@
-// Host-side launchers of the kernels in trace_kernel.hip (called by rt_render.cpp and rt_device.cpp).
+// Host-side launchers of the kernels in the .hip translation units (called by rt_render.cpp and
+// rt_device.cpp): trace_mega.hip, the wavefront schedule's wf_sequence.hip and, behind it, its
+// kernel families (wf_launch.hpp), wf_output.hip, probes.hip and path_kernel.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -59,7 +61,7 @@ hipError_t launch_trace_frame(const DevScene& sc, const FrameParams& fp, int mod
 // fold; the shadow + shading kernels of generation k run on b[k % nb] (b[i] ==
 // a: one in-order stream).  near_done: kMaxGenerations events; b_done: one
 // per b stream; marks may be null.  Sphere sources and the supported
-// (nearest, shadow) pairs: trace_kernel.hip kSrc* and launch_wavefront.
+// (nearest, shadow) pairs: wf_device.hpp kSrc* and wf_sequence.hip launch_wavefront.
 constexpr int kMaxBStreams = 4;
 struct WfStreams {
     hipStream_t a;
@@ -116,7 +118,8 @@ hipError_t launch_chain_segs(const FrameParams& fp, const WfBufs& b, uint32_t* s
 hipError_t launch_chain_pack(const FrameParams& fp, const uint32_t* segbits, const uint32_t* rowoff, uint8_t* pk_bgr,
                              float* pk_rgb, hipStream_t s);
 // rt_ctx_reserve: a no-op launch of `workgroups` 1024-thread workgroups with private memory
-// on stream s (loads trace_kernel.hip's code object, sets up the stream's queue and scratch);
+// on stream s (sets up the stream's queue and scratch), then an empty launch from every other
+// kernel translation unit but path_kernel.hip, so that each code object is loaded;
 // launch_path_warmup loads path_kernel.hip's.
 hipError_t launch_warmup(uint32_t workgroups, hipStream_t s);
 hipError_t launch_path_warmup(hipStream_t s);

@@ -427,7 +427,7 @@ int launch_chunks(rt_ctx* c, const rt_render_opts* o, RenderReq req, const Rende
         // rt_render_accumulate: passes S .. S + n - 1 (aa_pass: the global sample index, so aa_add's "pass 0
         // stores" is "the first sample stores") straight onto the accumulator's rows of the chunk (the sums
         // are tile-wide; a chunk addresses them by its first row); aa_spp is 0, which no pass number + 1
-        // reaches: launch_wavefront never runs the per-chunk wf_resolve
+        // reaches: launch_wavefront never runs the per-chunk accum_resolve
         const uint32_t passes = req.accumulate ? req.acc_n : p.aa ? f.aa_spp : 1u;
         for (uint32_t a = 0; a < passes; ++a) {
             const bool last = a + 1 == passes;

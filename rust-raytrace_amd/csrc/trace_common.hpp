@@ -1,5 +1,5 @@
 // Device-side exact restatement of the reference's per-ray math, shared by the
-// megakernel and the wavefront kernels (trace_kernel.hip) and the path kernel
+// megakernel (trace_mega.hip), the wavefront kernels (wf_*.hip) and the path kernel
 // (path_kernel.hip); the skybox sampler (background) has its one copy here.
 //
 // Exactness: every operation is the reference's f64 operation in the
@@ -18,7 +18,20 @@
 
 namespace rtamd {
 
-extern __constant__ double c_srgb_avg[255];
+// The sRGB quantisation table (host_color.cpp), one copy per code object that reads it: without
+// relocatable device code a translation unit's kernels see only its own.  Such a unit defines
+// RT_UNIT (its name) before its includes and gets its copy here, under a name of its own so that
+// the copies link into one library (upload_srgb_table fills them all: wf_launch.hpp,
+// RT_SRGB_UNITS).  External linkage on purpose: an internal table that the host also names is
+// addressed through the GOT, a load more in every kernel that reads it.
+#ifdef RT_UNIT
+#define RT_CAT_(a, b) a##b
+#define RT_CAT(a, b) RT_CAT_(a, b)
+#define c_srgb_avg RT_CAT(c_srgb_avg_, RT_UNIT)
+__constant__ double c_srgb_avg[255];
+#else
+extern __constant__ double c_srgb_avg[255];     // (a unit that never reads it)
+#endif
 
 constexpr double kMinSignificance = 1.0 / 256.0 / 2.0;            // raytrace.rs:17
 constexpr double kEps = 0.00001;                                   // raytrace.rs:43,62

@@ -23,7 +23,7 @@ namespace rtamd {
     X(Lgrid, "light_grids", 1, 0, 1)                                                                                 \
     /* 0: from the median sphere's angular size */                                                                   \
     X(LgridRes, "light_grid_res", 0, 0, 4096)                                                                        \
-    /* nearest-hit sphere source (trace_kernel.hip kSrc*) */                                                         \
+    /* nearest-hit sphere source (wf_device.hpp kSrc*) */                                                            \
     X(Src, "src", -1, -1, 26)                                                                                        \
     /* shadow sphere source */                                                                                       \
     X(SrcOcc, "src_occ", -1, -1, 26)                                                                                 \

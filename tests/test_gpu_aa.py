@@ -451,7 +451,7 @@ def test_kernel_times_count_a_camera_pass_per_sample_and_chunk(gpu_ctx, capfd):
         kt = gpu_ctx.kernel_times()
         assert kt["camera"][1] == 3 * 3
         assert kt["tally"][1] == 3 * 3                    # every pass tallies its own rays
-        assert kt["compose"][1] == 3 + 9 * compose        # wf_resolve per chunk (+ the row-ordered sums per pass)
+        assert kt["compose"][1] == 3 + 9 * compose        # accum_resolve per chunk (+ the row-ordered sums per pass)
 
 
 # ---- CLI ----

@@ -274,7 +274,7 @@ def test_axis_aligned_rays_and_ties_across_leaves(gpu_ctx, algo):
 
 @pytest.mark.parametrize("scene", ["axis_ties", "sphere_chain", "config3", "planes_nan", "fresnel"])
 def test_fused_tail_matches_oracle(gpu_ctx, scene):
-    """The fused tail (tuning tail_fuse = T, trace_kernel.hip wf_tail): every
+    """The fused tail (tuning tail_fuse = T, wf_tail.hip wf_tail): every
     chain still running at generation T-1 goes from its shade record through
     all its remaining bounces -- light-view grid shadows, Phong sum,
     reflection, nearest hit -- in one launch, one chain per work-item, and
@@ -687,7 +687,7 @@ def test_tuning_knobs_do_not_change_results(gpu_ctx):
 
 @pytest.mark.parametrize("compose", [1, 0])
 def test_row_ordered_compose_matches_oracle(gpu_ctx, compose):
-    """The row-ordered frame pass (tuning compose, trace_kernel.hip wf_compose):
+    """The row-ordered frame pass (tuning compose, wf_output.hip wf_compose):
     widths around the 64-pixel segment (1, 63, 64, 65, 130, 197), tight BGR rows
     (3 w bytes: byte stores) and dword-padded rows with extra slack (dword
     stores, the padding zeroed), misses, ambient ends and chains in one frame:

@@ -406,7 +406,7 @@ def test_chunked_passes_equal_one_chunk(gpu_ctx, capfd):
 
 def test_resolve_is_timed_as_compose(gpu_ctx, capfd):
     """RT_TIME_KERNELS on the accumulate: its passes' launches and the resolve after it (RT_KF_COMPOSE) are timed;
-    the per-chunk wf_resolve never runs."""
+    the per-chunk accum_resolve never runs."""
     spec = scenes.config3(96, 64, n=300)
     gpu_ctx.upload(lr.Scene.deserialize(spec.to_text()))
     for compose in (0, 1):

@@ -1,8 +1,9 @@
 """Per-basic-block instruction mix of one kernel in a hipcc -S listing, with the
 blocks that a backward branch reaches (loop heads) and the branches that close
 them marked.  Usage:
-    python3 tools/isa_loops.py build/trace_kernel.s <mangled-name-substring> [min_insts] [--dump BLOCK ...]
-Listing: hipcc -O3 --offload-arch=gfx950 --cuda-device-only -S csrc/trace_kernel.hip (same flags as the
+    python3 tools/isa_loops.py build/wf_nearest_bvh.s <mangled-name-substring> [min_insts] [--dump BLOCK ...]
+Listing: `make isa` (build/<unit>.s for every csrc/<unit>.hip), or hipcc -O3 --offload-arch=gfx950
+--cuda-device-only -S csrc/wf_nearest_bvh.hip for the one unit that has the kernel (same flags as the
 Makefile).  --dump prints the instructions of the named blocks (e.g. .LBB74_15)."""
 import re
 import sys

@@ -1,6 +1,6 @@
 """Register / scratch / LDS usage of the gfx950 kernels in a hipcc object or
 shared library (its .hip_fatbin offload bundle), from the code object's
-metadata notes.  Usage: python3 tools/kernel_meta.py build/trace_kernel.o [name-substring]"""
+metadata notes.  Usage: python3 tools/kernel_meta.py build/wf_tail.o [name-substring]   (any of build/*.o built from csrc/*.hip)"""
 import os
 import re
 import subprocess

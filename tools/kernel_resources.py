@@ -2,10 +2,11 @@
 """Compare the kernels' resources of two builds (DESIGN.md §3.12's table), no GPU needed.
 
 Each input is the stderr of
+    for f in rust-raytrace_amd/csrc/*.hip; do
     hipcc -O3 -std=c++17 --offload-arch=gfx950 -ffp-contract=off -fno-fast-math -Iinclude \\
-          -Irust-raytrace_amd/csrc -c rust-raytrace_amd/csrc/trace_kernel.hip -o /dev/null \\
-          -Rpass-analysis=kernel-resource-usage 2> LOG
-on one checkout (the same line on path_kernel.hip for the path kernel's pair).  Kernels are matched
+          -Irust-raytrace_amd/csrc -c $f -o /dev/null -Rpass-analysis=kernel-resource-usage; done 2> LOG
+on one checkout: the remark logs of all its translation units, one after the other (the parser
+goes line by line; a checkout from before the split has trace_kernel.hip and path_kernel.hip).  Kernels are matched
 by demangled name (c++filt); a trailing `false` template argument of wf_nearest / wf_fold / wf_tail / wf_shade /
 trace_frame_kernel / wf_compose / wf_aa_compose in the second build (a parameter the first build
 does not have; a kernel the first build has as a plain function loses its `<false>`) is dropped
