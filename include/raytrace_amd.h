@@ -21,6 +21,10 @@
  *   rt_render_accumulate / rt_accum_resolve
  *                         main.rs:47-56 split over calls: `res = res + raytrace(..)` for a range of the
  *                         AA samples, and `res / antialias` + write_bgr whenever a frame is wanted
+ *   rt_render_aov / rt_render_aov_device
+ *                         main.rs:39-56 with `raytrace(..)` replaced by what Scene::intersect (scene.rs:247-249)
+ *                         answers for the camera ray: Hit.t, the shape's normal (shapes.rs:72, 79, 108) and the
+ *                         hit object; no shading
  *   rt_scene_set_skybox   scene.rs:174-188       SkyboxBackground { px, nx, py, ny, pz, nz }
  *   rt_texture_load       texture.rs:34-37       Texture::load (BMP and binary PPM here; the image crate decodes more)
  *   rt_to_srgb            color.rs:593-600       fn to_srgb (used by Color::write_bgr, color.rs:628-632)
@@ -57,7 +61,10 @@
 extern "C" {
 #endif
 
-/* 8: rt_cull_check and rt_cull_reach added (diagnostics of the conservative f32 culling and of the
+/* 9: first-hit feature buffers: enum rt_aov, rt_aov_buffers, rt_render_aov and rt_render_aov_device
+ * (depth, normal, albedo, coverage and object id of the camera rays' first hits).  Functions and types
+ * added only: no struct, enum value or tuning key changed, RT_KF_COUNT is still 8.
+ * 8: rt_cull_check and rt_cull_reach added (diagnostics of the conservative f32 culling and of the
  * far-origin rule).  No struct, enum value or tuning key changed.
  * 7: progressive rendering: rt_accum (a device-resident f64 accumulator of one tile) with
  * rt_accum_create / destroy / samples / reset, rt_render_accumulate, rt_accum_resolve / resolve_host,
@@ -78,7 +85,7 @@ extern "C" {
  * 4: rt_abi_version() added; RT_KF_TAIL (RT_KF_COUNT 8).  A caller checks
  * rt_abi_version() == RT_ABI_VERSION of the header it was built against before
  * passing any struct; any change of a struct, enum value or tuning key bumps it. */
-#define RT_ABI_VERSION 8
+#define RT_ABI_VERSION 9
 
 enum rt_status {
     RT_OK = 0,
@@ -333,6 +340,49 @@ int rt_ctx_reserve(rt_ctx* ctx, const rt_render_opts* opts, int host, void* stre
  * or frees), rt_ctx_set_tuning (also of the keys that rebuild the streams) and
  * rt_scene_upload of another scene: the next render replaces them, nothing else. */
 int rt_ctx_stats(rt_ctx* ctx, rt_stats* stats);
+/* ---- first-hit feature buffers (AOVs) ----
+ * What Scene::intersect (scene.rs:223-249) answers for the camera rays, averaged over the AA samples as colours
+ * are (main.rs:47-56), without any shading.  For tile pixel (x, local row j) and AA sample a in [0, spp):
+ *   ray_a = the camera ray rt_render traces for (x, j, a): the pixel mapping of main.rs:39-41, 50-53 from the
+ *           geometry fields of rt_render_opts, jitter and seed (RT_JITTER_CENTER: jx = jy = 0.5; RT_JITTER_RANDOM:
+ *           the keyed draws of sample a), then camera.rs:78.  Under RT_JITTER_RANDOM the buffers line up sample for
+ *           sample with the colours RT_ALGO_PATH and RT_ALGO_WAVEFRONT_AA render.
+ *   h_a   = Scene::intersect(ray_a): the smallest t, the first object in file order on a tie, and a NaN t (only a
+ *           plane's 0/0 gives one) beats everything (scene.rs:223-249).
+ * Per-sample values v_a:            hit                                                          miss
+ *   depth                           h.t                                                          0.0
+ *   normal x, y, z                  the shape's normal: sphere normalize(ray.cast(t) - centre)   0.0, 0.0, 0.0
+ *                                   (shapes.rs:72, 79), plane as in the file, not normalised
+ *                                   (shapes.rs:108); negated when dot(normal, ray.direction)
+ *                                   > 0.0 (the rule of raytrace.rs:38, here for every material)
+ *   albedo r, g, b                  the hit object's `diffuse` as rt_scene_get_desc reports      0.0, 0.0, 0.0
+ *                                   it, whatever its material
+ *   coverage                        1.0                                                          0.0
+ * Every float channel is averaged as main.rs:47-56 averages colours: sum = 0.0; sum = sum + v_a for a = 0 .. spp-1
+ * in sample order; out = (float)(sum / (double)spp): one rounding to f32, NaN propagates (a plane's NaN t gives a
+ * NaN depth and leaves the other channels finite).  With RT_JITTER_CENTER the samples are identical: the ray is
+ * traced once and the sum still formed with spp additions.  The mean of a channel over the samples that hit is
+ * channel / coverage.
+ * object (int32): the object id (file order, what Hit::obj holds) of sample 0's hit, -1 when sample 0 misses.
+ *
+ * Buffers are tile row-major, tile_h rows of tile_w elements (normal and albedo: 3 floats per pixel); local row
+ * j is frame row y0 + ((j/band)*band_stride + band_phase)*band + j%band as for rt_render.  Read of opts: width,
+ * height, x0, tile_w, y0, tile_h, band, band_stride, band_phase, spp (0: the scene's), jitter, seed, and of flags
+ * RT_TIME_KERNELS alone (the launch's time is counted under RT_KF_CAMERA); max_depth, algo, the other flags and
+ * bgr_pitch are ignored (no RT_OUT_FRAME_ROWS).  channels: a non-empty mask of rt_aov; only the selected buffers
+ * are read from the struct and written.
+ * RT_E_INVALID: channels 0 or with unknown bits, a selected channel whose pointer is NULL, tile geometry that
+ * rt_render would refuse; RT_E_NOSCENE: no scene uploaded; RT_E_UNSUPPORTED: a DepthOfFieldCamera (its rays go
+ * through cos and sin: not a bit-exact feature).  Every other scene class is served.
+ * An AOV render is a render of the context: ordered on the device after the previous one; afterwards rt_ctx_stats
+ * reports rays = pixels * spp, shadow_rays 0, pixels, chunks 0 and traced_rays = pixels under RT_JITTER_CENTER,
+ * else rays.  A refused call is no render: the statistics stay the previous render's. */
+enum rt_aov { RT_AOV_DEPTH = 1, RT_AOV_NORMAL = 2, RT_AOV_ALBEDO = 4, RT_AOV_COVERAGE = 8, RT_AOV_OBJECT = 16 };
+typedef struct { float* depth; float* normal; float* albedo; float* coverage; int32_t* object; } rt_aov_buffers;
+/* Synchronous, into caller-owned HOST buffers. */
+int rt_render_aov(rt_ctx* ctx, const rt_render_opts* opts, uint32_t channels, const rt_aov_buffers* host, rt_stats* stats);
+/* Asynchronous on `stream` (NULL: the context's own), into caller-owned DEVICE buffers. */
+int rt_render_aov_device(rt_ctx* ctx, const rt_render_opts* opts, uint32_t channels, const rt_aov_buffers* dev, void* stream);
 /* ---- progressive rendering (main.rs:47-56 split over calls) ----
  * The reference's pixel is `res = BLACK; for _ in 0..antialias { res = res + raytrace(..) }; res / antialias`
  * (main.rs:47-56).  An rt_accum keeps `res` of every pixel of one tile on the device between calls: f64
@@ -445,7 +495,7 @@ enum rt_kernel_family {
     RT_KF_SHADE = 2,        /* wf_shade */
     RT_KF_FOLD = 3,         /* wf_fold */
     RT_KF_TALLY = 4,        /* wf_tally */
-    RT_KF_CAMERA = 5,       /* wf_nearest, generation 0 (camera rays) */
+    RT_KF_CAMERA = 5,       /* wf_nearest, generation 0 (camera rays); aov_primary of an RT_TIME_KERNELS AOV render */
     RT_KF_COMPOSE = 6,      /* wf_compose: the row-ordered frame pass (tuning compose); RT_ALGO_WAVEFRONT_AA:
                                accum_resolve after a chunk's last pass (and wf_aa_compose per pass, tuning compose);
                                accum_resolve of an rt_accum_resolve after an RT_TIME_KERNELS rt_render_accumulate;

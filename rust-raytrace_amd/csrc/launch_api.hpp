@@ -1,6 +1,6 @@
 // Host-side launchers of the kernels in the .hip translation units (called by rt_render.cpp and
 // rt_device.cpp): trace_mega.hip, the wavefront schedule's wf_sequence.hip and, behind it, its
-// kernel families (wf_launch.hpp), wf_output.hip, probes.hip and path_kernel.hip.
+// kernel families (wf_launch.hpp), wf_output.hip, wf_aov.hip, probes.hip and path_kernel.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -130,6 +130,21 @@ hipError_t launch_sqrt_probe(const double* x, uint32_t n, double* fast, double* 
 // Diagnostic: the tree walks' f32 culling arithmetic on n (ray, box, t, code) records (rt_cull_check).
 hipError_t launch_cull_probe(uint32_t n, const double* rays, const float* boxes, const double* t, const int32_t* codes,
                              float reach, int32_t* out_i, float* out_f, hipStream_t s);
+
+// First-hit feature buffers (wf_aov.hip, rt_render_aov): device buffers of the tile, tile row-major; null: the
+// channel is not selected and costs nothing.  normal and albedo: 3 floats per pixel.
+struct AovOut {
+    float* depth;
+    float* normal;
+    float* albedo;
+    float* coverage;
+    int32_t* object;
+};
+// aov_primary from sphere source src (render_plan.hpp, plan_aov_source; an unknown one: hipErrorInvalidValue) over the
+// whole tile of fp (fp.spp samples per pixel, fp.jitter, fp.seed), `workgroups` workgroups of kWfThreads; each
+// workgroup adds its pixels * fp.spp to a shard of fp.counters (the rays of the render).
+hipError_t launch_aov(const DevScene& sc, const FrameParams& fp, const AovOut& out, int src, uint32_t workgroups,
+                      hipStream_t s);
 
 // The general path (path_kernel.hip): every material / light / camera class,
 // keyed random draws, one work-item per pixel over the HBM recursion stack.

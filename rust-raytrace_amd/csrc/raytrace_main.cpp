@@ -10,8 +10,13 @@
 //   raytrace [--scene FILE] [--out FILE] [--width W] [--height H] [--spp N]
 //            [--max-depth D] [--gpus N] [--band ROWS] [--jitter random|center] [--seed N]
 //            [--algo auto|wavefront|wavefront-aa|path|lds|global]
-//            [--progressive K] [--checkpoint FILE]
+//            [--progressive K] [--checkpoint FILE] [--aov PREFIX]
 //
+// --aov PREFIX: instead of the image, the first-hit feature buffers of the frame (rt_render_aov; --spp, --jitter,
+// --seed, --width, --height apply) as PFM files (portable float map: "PF" 3 channels / "Pf" 1 channel, width
+// height, scale -1.0 = little-endian, rows bottom-up, which is the library's row order): PREFIX.depth.pfm,
+// PREFIX.normal.pfm, PREFIX.albedo.pfm, PREFIX.coverage.pfm and PREFIX.object.pfm (the id as a float; ids are
+// below 2^24).  Single-device.
 // --progressive K: the frame's samples in steps of K (rt_render_accumulate; main.rs:47-56 split over
 // calls); after every step --out is rewritten (a temporary name, renamed) with the image of the samples
 // so far and "samples done/total" goes to stderr.  --checkpoint FILE: FILE is written after every step
@@ -43,6 +48,7 @@ struct Args {
     unsigned long long seed = 1;       // keyed draws (the reference seeds from OS entropy, main.rs:43)
     long progressive = 0;              // samples per step (0: one render)
     std::string checkpoint;
+    std::string aov;                   // --aov PREFIX: write the feature buffers instead of the image
 };
 
 bool parse_args(int argc, char** argv, Args& a) {
@@ -61,6 +67,7 @@ bool parse_args(int argc, char** argv, Args& a) {
         else if (k == "--seed" && (v = val())) a.seed = std::strtoull(v, nullptr, 0);
         else if (k == "--progressive" && (v = val())) a.progressive = std::atol(v);
         else if (k == "--checkpoint" && (v = val())) a.checkpoint = v;
+        else if (k == "--aov" && (v = val())) a.aov = v;
         else if (k == "--jitter" && (v = val())) a.jitter = std::string(v) == "center" ? RT_JITTER_CENTER : RT_JITTER_RANDOM;
         else if (k == "--algo" && (v = val())) {
             std::string s = v;
@@ -71,7 +78,7 @@ bool parse_args(int argc, char** argv, Args& a) {
             std::fprintf(stderr, "usage: raytrace [--scene FILE] [--out FILE] [--width W] [--height H] [--spp N]\n"
                                  "                [--max-depth D] [--gpus N] [--band ROWS] [--jitter random|center]\n"
                                  "                [--seed N] [--algo auto|wavefront|wavefront-aa|path|lds|global]\n"
-                                 "                [--progressive K] [--checkpoint FILE]\n");
+                                 "                [--progressive K] [--checkpoint FILE] [--aov PREFIX]\n");
             return false;
         }
     }
@@ -176,6 +183,48 @@ int run_progressive(const Args& a, rt_scene* scene, const std::string& text, uin
     return done_with(0);
 }
 
+// One PFM file: `channels` (1 or 3) floats per pixel, rows in the library's order (row 0 = the image bottom).
+bool write_pfm(const std::string& path, uint32_t W, uint32_t H, int channels, const float* data) {
+    std::FILE* f = std::fopen(path.c_str(), "wb");
+    if (!f) return false;
+    const size_t n = static_cast<size_t>(W) * H * channels;
+    bool ok = std::fprintf(f, "%s\n%u %u\n-1.0\n", channels == 3 ? "PF" : "Pf", W, H) > 0;
+    ok = ok && std::fwrite(data, sizeof(float), n, f) == n;
+    return (std::fclose(f) == 0) && ok;
+}
+
+// --aov PREFIX: one device, the whole frame, every channel.
+int run_aov(const Args& a, rt_scene* scene, uint32_t W, uint32_t H, uint32_t spp) {
+    rt_ctx* ctx = nullptr;
+    if (rt_ctx_create(0, &ctx) != RT_OK) { std::printf("error: %s\n", rt_last_error(nullptr)); return 1; }
+    auto done_with = [&](int code) {
+        rt_ctx_destroy(ctx);
+        return code;
+    };
+    if (rt_scene_upload(ctx, scene) != RT_OK) { std::printf("error: %s\n", rt_last_error(ctx)); return done_with(1); }
+    rt_render_opts o;
+    rt_render_opts_default(&o, W, H);
+    o.spp = spp; o.jitter = a.jitter; o.seed = a.seed;
+    const size_t n = static_cast<size_t>(W) * H;
+    std::vector<float> depth(n), normal(3 * n), albedo(3 * n), coverage(n), idf(n);
+    std::vector<int32_t> object(n);
+    const rt_aov_buffers b{depth.data(), normal.data(), albedo.data(), coverage.data(), object.data()};
+    rt_stats st{};
+    const uint32_t all = RT_AOV_DEPTH | RT_AOV_NORMAL | RT_AOV_ALBEDO | RT_AOV_COVERAGE | RT_AOV_OBJECT;
+    if (rt_render_aov(ctx, &o, all, &b, &st) != RT_OK) { std::printf("error: %s\n", rt_last_error(ctx)); return done_with(1); }
+    for (size_t i = 0; i < n; ++i) idf[i] = static_cast<float>(object[i]);
+    const struct { const char* name; int channels; const float* data; } files[] = {
+        {"depth", 1, depth.data()}, {"normal", 3, normal.data()}, {"albedo", 3, albedo.data()},
+        {"coverage", 1, coverage.data()}, {"object", 1, idf.data()}};
+    for (const auto& f : files) {
+        const std::string path = a.aov + "." + f.name + ".pfm";
+        if (!write_pfm(path, W, H, f.channels, f.data)) { std::printf("error: cannot write %s\n", path.c_str()); return done_with(1); }
+    }
+    std::fprintf(stderr, "%ux%u spp=%u aov: %llu rays, kernel %.3f ms\n", W, H, spp, static_cast<unsigned long long>(st.rays),
+                 st.kernel_ms);
+    return done_with(0);
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -200,6 +249,20 @@ int main(int argc, char** argv) {
     int ndev = 0;
     rt_device_count(&ndev);
     if (ndev < 1) { std::printf("error: no GPU\n"); return 1; }
+    if (!a.aov.empty()) {
+        if (a.gpus > 1) {
+            std::printf("error: --aov renders on one device: not with --gpus %d\n", a.gpus);
+            return 2;
+        }
+        if (a.progressive > 0 || !a.checkpoint.empty()) {
+            std::printf("error: --aov writes the feature buffers of one render: not with --progressive or --checkpoint\n");
+            return 2;
+        }
+        if (spp == 0) { std::printf("error: --spp is 0 and the scene's antialias is 0\n"); return 1; }
+        const int rc = run_aov(a, scene, W, H, spp);
+        rt_scene_free(scene);
+        return rc;
+    }
     if (a.progressive > 0 || !a.checkpoint.empty()) {
         if (a.gpus > 1) {
             std::printf("error: --progressive and --checkpoint render on one device: not with --gpus %d\n", a.gpus);

@@ -158,6 +158,47 @@ SourcePair plan_sources(const SceneFacts& sf, const int64_t* tune, int mode) {
     return p;
 }
 
+AovSource plan_aov_source(const SceneFacts& sf, const int64_t* tune) {
+    AovSource a;
+    int64_t t[kTuneCount];
+    for (int i = 0; i < kTuneCount; ++i) t[i] = tune[i];
+    t[kTuneQTree] = 0;
+    int64_t forced = t[kTuneSrc];
+    if (forced == 25 || forced == 26) forced = t[kTuneSrc] = -1;
+    // src alone selects: the shadow source plan_sources pairs it with
+    if (forced >= 0) t[kTuneSrcOcc] = forced == 9 ? 10 : forced == 5 || forced == 6 || forced == 8 ? 11 : forced;
+    const SourcePair sp = plan_sources(sf, t, RT_ALGO_WAVEFRONT);
+    a.pfx2 = sp.pfx2;
+    const size_t list_bytes = static_cast<size_t>(sf.n_spheres) * (sizeof(DevSphere) + sizeof(int32_t));
+    const int brute = static_cast<size_t>(sf.n_spheres) * sizeof(DevSphere) <= 64 * 1024 ? 1 : 0;
+    if ((t[kTuneCam] == 3 || t[kTuneCam] < 0) && sf.has_cgrid) a.src = list_bytes <= kLdsBudget ? 22 : 23;
+    else if (forced == 0 || forced == 1 || sf.n_bvh == 0) a.src = forced == 0 ? 0 : brute;
+    else a.src = sp.src;
+    return a;
+}
+
+int plan_aov_args(uint32_t channels, const void* const ptrs[5], const char** err) {
+    if (channels == 0) {
+        *err = "rt_render_aov: no channel selected";
+        return RT_E_INVALID;
+    }
+    if (channels & ~kAovAll) {
+        *err = "rt_render_aov: unknown channel bits";
+        return RT_E_INVALID;
+    }
+    for (int i = 0; i < 5; ++i)
+        if (((channels >> i) & 1u) && !ptrs[i]) {
+            *err = "rt_render_aov: a selected channel's buffer is NULL";
+            return RT_E_INVALID;
+        }
+    return RT_OK;
+}
+
+uint32_t plan_aov_workgroups(uint64_t npix, int n_cu) {
+    const uint64_t need = (npix + kWfThreads - 1) / kWfThreads;
+    return static_cast<uint32_t>(std::max<uint64_t>(1, std::min<uint64_t>(need, 2ull * static_cast<uint64_t>(std::max(n_cu, 1)))));
+}
+
 StreamShape plan_streams(const SceneFacts& sf, const int64_t* tune, int mode, int src, uint32_t max_depth) {
     StreamShape s;
     // tuning "split" 0: every kernel on one in-order stream (A/B measurement);

@@ -80,6 +80,33 @@ struct SourcePair {
 };
 SourcePair plan_sources(const SceneFacts& sf, const int64_t* tune, int mode);
 
+// ---- first-hit feature buffers (rt_render_aov) ----------------------------------------------
+// The sphere source of aov_primary (wf_aov.hip), one camera ray per sample and pixel:
+//   the camera's view grid where the scene has one (22 spheres in LDS, 23 through L2), as generation 0 takes it
+//     (tuning cam 3 or -1; any other value: off);
+//   else the source the wavefront's later generations take for this tree (plan_sources): the whole tree in LDS
+//     (7, 9), an LDS prefix beyond it (5, 6, 8), the binary tree through L2 (2) where neither applies;
+//   else (a scene without spheres' tree, or tuning src 0 / 1) brute force, the sphere list from LDS (1) when it
+//     fits 64 KB, else through the caches (0).
+// Tuning src forces a family as it does for the wavefront; its shadow partner (src_occ) is of no concern here and
+// is filled in, so that src alone selects.  The quantised tree (25, 26, tuning qtree) has no AOV instantiation:
+// such a request takes what the scene would get without it.  pfx2: DevScene::pfx2 for the prefix sources.
+struct AovSource {
+    int src = 0;
+    int32_t pfx2 = 0;
+};
+AovSource plan_aov_source(const SceneFacts& sf, const int64_t* tune);
+// Whether aov_primary has an instantiation for sphere source src (launch_aov's cases).
+constexpr bool aov_source_known(int src) {
+    return src == 0 || src == 1 || src == 2 || (src >= 5 && src <= 9) || src == 22 || src == 23;
+}
+// The call's argument checks that need no device: channels a non-empty mask of rt_aov, every selected pointer set.
+// ptrs: depth, normal, albedo, coverage, object.  RT_OK or RT_E_INVALID with its text in *err.
+constexpr uint32_t kAovAll = 31u;
+int plan_aov_args(uint32_t channels, const void* const ptrs[5], const char** err);
+// Workgroups of the launch: one 1024-thread workgroup per 1024 pixels, at most two per CU (all resident).
+uint32_t plan_aov_workgroups(uint64_t npix, int n_cu);
+
 // ---- streams ----------------------------------------------------------------------------
 struct StreamShape {
     bool split = false;     // shadow + shading kernels on b streams of their own

@@ -1,7 +1,8 @@
 // The device context behind the C ABI (include/raytrace_amd.h), its error helpers, and what the
 // translation units that implement it share: rt_device.cpp (create / destroy, tuning, probes),
 // rt_scene_upload.cpp, rt_render.cpp (the render path, lanes, reserve, statistics), rt_accum.cpp
-// (progressive rendering: the accumulator and its calls) and rt_copy.cpp (device -> host copies).
+// (progressive rendering: the accumulator and its calls), rt_aov.cpp (first-hit feature buffers: the entry
+// points' checks and the host variant) and rt_copy.cpp (device -> host copies).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -244,6 +245,10 @@ int check_join_error(rt_ctx* c);
 // rt_render_accumulate behind its argument checks: one render of o's tile (o: the accumulator's bound options
 // with the call's algo and flags) that adds samples [first, first + n) to `sums`.  n == 0: the checks only.
 int render_accumulate(rt_ctx* c, const rt_render_opts* o, double* sums, uint32_t first, uint32_t n, void* stream);
+
+// rt_render_aov behind its argument checks: one render of o's tile into the selected device buffers of `out`
+// (channels: the rt_aov mask, for the verbose line) on `stream` (null: the context's own).
+int render_aov(rt_ctx* c, const rt_render_opts* o, const AovOut& out, uint32_t channels, void* stream);
 
 // ---- rt_accum.cpp -------------------------------------------------------------------------
 // rt_ctx_destroy: free the device memory of the accumulators still alive and detach them.

@@ -748,6 +748,44 @@ int render_accumulate(rt_ctx* c, const rt_render_opts* o, double* sums, uint32_t
     return render_device(c, o, nullptr, nullptr, stream, req);
 }
 
+// rt_render_aov / rt_render_aov_device behind their argument checks (rt_aov.cpp): a render of the context like
+// every other (begin_render: the geometry checks rt_render makes, the stream's wait for the previous render;
+// end_render), one launch of aov_primary from the source the planner names.  The fields an AOV render ignores
+// (max_depth, algo, bgr_pitch, flags but RT_TIME_KERNELS) do not reach the checks.
+int render_aov(rt_ctx* c, const rt_render_opts* o, const AovOut& out, uint32_t channels, void* stream) {
+    rt_render_opts b = *o;
+    b.max_depth = 0; b.algo = RT_ALGO_AUTO; b.bgr_pitch = 0; b.flags = 0;
+    RenderCall rcall;
+    if (const int rc = begin_render(c, &b, nullptr, nullptr, stream, rcall); rc != RT_OK) return rc;
+    const hipStream_t st = rcall.st;
+    const AovSource as = plan_aov_source(scene_facts(c), c->tune);
+    c->dsc.pfx2 = as.pfx2;
+    const uint64_t npix = static_cast<uint64_t>(o->tile_w) * o->tile_h;
+    c->tally.on = false;
+    c->last_pixels = npix;
+    c->last_stream = st;
+    // centre jitter: one of the spp identical samples is traced and counted spp times
+    c->last_spp_traced = o->jitter == RT_JITTER_CENTER ? rcall.spp : 1;
+    c->last_chunks = 0;
+    c->n_bands = 0;
+    c->sparse_on = false;
+    if (const int rc = zero_counters(c, st); rc != RT_OK) return rc;
+    if (c->t(kTuneVerbose))
+        std::fprintf(stderr, "rtamd: aov src %d spp %u channels 0x%x pixels %llu\n", as.src, rcall.spp, channels,
+                     static_cast<unsigned long long>(npix));
+    c->ev0_set = true;
+    HIP_TRY(c, hipEventRecord(c->ev0, st));
+    if (npix) {
+        const bool timed = (o->flags & RT_TIME_KERNELS) != 0;
+        LaunchMarks m;
+        m.pool = &c->tev; m.used = &c->t_used; m.out = &c->tint;
+        if (timed) HIP_TRY(c, m.begin(st));
+        HIP_TRY(c, launch_aov(c->dsc, rcall.fp, out, as.src, plan_aov_workgroups(npix, c->n_cu), st));
+        if (timed) HIP_TRY(c, m.mark(st, kKfCamera));
+    }
+    return end_render(c, st, true);
+}
+
 void drop_lanes(rt_ctx* c) {
     for (auto& L : c->lanes) {
         release_lane_memory(c, L);

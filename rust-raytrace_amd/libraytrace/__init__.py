@@ -20,7 +20,7 @@ PKG_DIR = os.path.dirname(_HERE)
 LIB_PATH = os.environ.get("RT_LIBRTAMD") or os.path.join(PKG_DIR, "librtamd.so")
 HEADER_PATH = os.path.join(os.path.dirname(PKG_DIR), "include", "raytrace_amd.h")
 
-RT_ABI_VERSION = 8               # include/raytrace_amd.h
+RT_ABI_VERSION = 9               # include/raytrace_amd.h
 RT_OK = 0
 RT_E_INVALID, RT_E_NODEVICE, RT_E_HIP, RT_E_NOMEM = -1, -2, -3, -4
 RT_E_UNSUPPORTED, RT_E_PARSE, RT_E_NOSCENE, RT_E_IO = -5, -6, -7, -8
@@ -35,6 +35,12 @@ RT_ALGO_AUTO, RT_ALGO_BRUTE_LDS, RT_ALGO_BRUTE_GLOBAL, RT_ALGO_WAVEFRONT, RT_ALG
 RT_ALGO_PATH = 5
 RT_ALGO_WAVEFRONT_AA = 6        # one wavefront pass per jittered AA sample
 RT_JITTER_CENTER, RT_JITTER_RANDOM = 0, 1
+RT_AOV_DEPTH, RT_AOV_NORMAL, RT_AOV_ALBEDO, RT_AOV_COVERAGE, RT_AOV_OBJECT = 1, 2, 4, 8, 16     # rt_aov
+RT_AOV_ALL = 31
+# rt_aov bit -> (rt_aov_buffers field, elements per pixel, dtype)
+AOV_CHANNELS = {RT_AOV_DEPTH: ("depth", 1, np.float32), RT_AOV_NORMAL: ("normal", 3, np.float32),
+                RT_AOV_ALBEDO: ("albedo", 3, np.float32), RT_AOV_COVERAGE: ("coverage", 1, np.float32),
+                RT_AOV_OBJECT: ("object", 1, np.int32)}
 RT_MAX_DEPTH_LIMIT = 30
 
 
@@ -89,6 +95,11 @@ class rt_stats(C.Structure):
                 ("chunks", C.c_uint64)]
 
 
+class rt_aov_buffers(C.Structure):
+    _fields_ = [("depth", C.c_void_p), ("normal", C.c_void_p), ("albedo", C.c_void_p), ("coverage", C.c_void_p),
+                ("object", C.c_void_p)]
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise ImportError(f"{LIB_PATH} is missing: run `make -C rust-raytrace_amd` "
@@ -119,6 +130,8 @@ def _load():
         "rt_render_device": (C.c_int, [C.c_void_p, P(rt_render_opts), C.c_void_p, C.c_void_p, C.c_void_p]),
         "rt_ctx_reserve": (C.c_int, [C.c_void_p, P(rt_render_opts), C.c_int, C.c_void_p]),
         "rt_ctx_stats": (C.c_int, [C.c_void_p, P(rt_stats)]),
+        "rt_render_aov": (C.c_int, [C.c_void_p, P(rt_render_opts), C.c_uint32, P(rt_aov_buffers), P(rt_stats)]),
+        "rt_render_aov_device": (C.c_int, [C.c_void_p, P(rt_render_opts), C.c_uint32, P(rt_aov_buffers), C.c_void_p]),
         "rt_accum_create": (C.c_int, [C.c_void_p, P(rt_render_opts), P(C.c_void_p)]),
         "rt_accum_destroy": (None, [C.c_void_p]),
         "rt_accum_samples": (C.c_int, [C.c_void_p, P(C.c_uint32)]),
@@ -459,6 +472,40 @@ class Context:
         """Asynchronous render into device buffers (raw pointers, e.g. torch tensor.data_ptr())."""
         _check(lib.rt_render_device(self._h, C.byref(opts), C.c_void_p(d_rgb_ptr or 0),
                                     C.c_void_p(d_bgr_ptr or 0), C.c_void_p(stream_ptr or 0)), self._h)
+
+    def render_aov(self, opts, channels=RT_AOV_ALL, out=None, stats=True):
+        """rt_render_aov: the first-hit feature buffers of opts' tile (synchronous) -> ({name: array}, stats).
+        Arrays: depth, coverage float32 [tile_h, tile_w]; normal, albedo float32 [tile_h, tile_w, 3]; object
+        int32 [tile_h, tile_w]; only the selected channels.  out: {name: array} to write into instead (a
+        selected channel missing from it is passed as NULL: the call is refused)."""
+        arrays, bufs = {}, rt_aov_buffers()
+        for bit, (name, n, dt) in AOV_CHANNELS.items():
+            if out is not None:
+                a = out.get(name)
+                if a is not None:
+                    assert a.dtype == dt and a.size >= opts.tile_h * opts.tile_w * n and a.flags.c_contiguous
+            elif channels & bit:
+                a = np.zeros((opts.tile_h, opts.tile_w) + ((n,) if n > 1 else ()), dt)
+            else:
+                a = None
+            if a is not None:
+                arrays[name] = a
+                setattr(bufs, name, a.ctypes.data)
+        st = rt_stats() if stats else None
+        _check(lib.rt_render_aov(self._h, C.byref(opts), int(channels), C.byref(bufs), C.byref(st) if stats else None),
+               self._h)
+        return arrays, st
+
+    def render_aov_device(self, opts, channels, ptrs, stream_ptr=None):
+        """rt_render_aov_device: asynchronous, into device buffers; ptrs: {name: raw device pointer} (e.g. torch
+        tensor.data_ptr()) for the channels' names depth, normal, albedo, coverage, object."""
+        bufs = rt_aov_buffers()
+        for name, ptr in ptrs.items():
+            if name not in [v[0] for v in AOV_CHANNELS.values()]:
+                raise TypeError(f"unknown AOV channel {name}")
+            setattr(bufs, name, ptr or None)
+        _check(lib.rt_render_aov_device(self._h, C.byref(opts), int(channels), C.byref(bufs), C.c_void_p(stream_ptr or 0)),
+               self._h)
 
     def reserve(self, opts, host=False, stream_ptr=None):
         """rt_ctx_reserve: allocate and warm up everything a render with opts needs (host: rt_render's

@@ -1,0 +1,167 @@
+"""The Python model of the first-hit feature buffers (tests/aov_model.py) pinned against the oracle,
+before any device is compared with it (test_gpu_aov.py); no GPU.
+
+For each scene the flat scene is rendered by the oracle: same geometry, camera and size, every object
+phong(diffuse 0, specular 0, exponent 1, ambient A_i), no lights, solid black background.  By
+raytrace.rs:32-36 its pixel is exactly sum(A of the sample's hit, or 0) / spp, so
+    A_i = diffuse_i             pins the model's albedo,
+    A_i = (1, 1, 1)             its coverage,
+    A_i = (i + 1, 0, 0), spp 1  its object id (sample 0 does not depend on the sample count: the key holds none),
+each required equal in every bit of every pixel, for (spp, jitter) in {(1, centre), (3, centre), (4, random)}.
+Depth and normal are the oracle's own sphere_intersect / plane_intersect results for the winner; the numpy
+restatement of the sphere quadratic that produces them is compared here with ref64.sphere_intersect on every
+ray of two scenes, bit for bit.
+
+Also here: the planner's cases (tests/native/aov_plan_check.cpp, built with sanitizers as a stand-alone
+program, as test_native_progressive.py builds its own), and what the entry points answer without a device.
+"""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import libraytrace as lr
+from libraytrace import scenes
+from oracle import ref64
+
+import aov_model as am
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "rust-raytrace_amd", "csrc")
+NATIVE = os.path.join(ROOT, "tests", "native")
+CXXFLAGS = ["-std=c++17", "-Wall", "-Wextra", "-Werror", "-ffp-contract=off", "-O1", "-g", "-I" + CSRC,
+            "-I" + os.path.join(ROOT, "include")]
+SAN = ["-fno-omit-frame-pointer", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"]
+
+
+@pytest.fixture(scope="module")
+def specs(tmp_path_factory):
+    d = tmp_path_factory.mktemp("aov_sky")
+    paths = [str(d / f"f{k}.ppm") for k in range(6)]
+    for p, f in zip(paths, scenes.skybox_faces(size=8, seed=2)):
+        scenes.write_ppm(p, f)
+    return am.scene_list(paths)
+
+
+def same_bits(a, b):
+    """float arrays equal in every bit, NaNs by position (IEEE leaves a NaN's sign and payload open)."""
+    a, b = np.asarray(a, np.float32), np.asarray(b, np.float32)
+    na, nb = np.isnan(a), np.isnan(b)
+    return a.shape == b.shape and np.array_equal(na, nb) and np.array_equal(am.bits(a)[~na], am.bits(b)[~nb])
+
+
+def oracle_f32(flat, jitter, seed):
+    return ref64.render(flat, max_depth=1, jitter=jitter, rng=1, seed=seed)["rgb64"].astype(np.float32)
+
+
+@pytest.mark.parametrize("name", am.SCENE_NAMES)
+def test_model_matches_the_oracle_on_flat_scenes(specs, name):
+    spec = specs[name]
+    for spp, jitter in am.CASES:
+        for seed in (am.SEEDS if jitter == am.RANDOM else am.SEEDS[:1]):
+            m = am.aov(spec, spp, jitter, seed)
+            alb = oracle_f32(am.flat_albedo(spec, spp), jitter, seed)
+            assert same_bits(alb, m["albedo"]), (name, spp, jitter, seed, "albedo")
+            cov = oracle_f32(am.flat_coverage(spec, spp), jitter, seed)
+            for ch in range(3):
+                assert same_bits(cov[:, :, ch], m["coverage"]), (name, spp, jitter, seed, "coverage")
+            ids = oracle_f32(am.flat_object(spec), jitter, seed)
+            assert np.array_equal(ids[:, :, 0], (m["object"] + 1).astype(np.float32)), (name, spp, jitter, seed, "object")
+            assert not ids[:, :, 1:].any()
+            # the channels agree with each other: coverage 0 <=> every sample missed
+            miss = m["coverage"] == 0
+            assert not m["albedo"][miss].any() and not m["normal"][miss].any() and not m["depth"][miss].any()
+            assert np.array_equal(m["object"] < 0, am.samples(spec, jitter, seed, 1)[0]["coverage"] == 0)
+
+
+def test_scenes_cover_what_they_are_for(specs):
+    """NaN depths with finite other channels, flipped normals through the t2 branch, ties, misses, partial coverage."""
+    nan = am.aov(specs["nan_plane"], 1, am.CENTER, 0)
+    assert np.isnan(nan["depth"]).any() and not np.isnan(nan["normal"]).any() and not np.isnan(nan["albedo"]).any()
+    assert (nan["coverage"][np.isnan(nan["depth"])] == 1).all()
+    inside = am.aov(specs["inside"], 1, am.CENTER, 0)
+    assert (inside["coverage"] == 1).all() and (inside["object"] == 0).sum() > 100      # the enclosing sphere, from within
+    o, d = am.camera_rays(specs["inside"], am.CENTER, 0, 0)
+    dots = (inside["normal"].astype(np.float64) * d).sum(axis=2)
+    assert (dots < 0).all()                                   # every normal faces the camera after the flip
+    tie = am.aov(specs["axis_tie"], 1, am.CENTER, 0)
+    assert (tie["object"] == 0).sum() > 10                    # 24 coincident spheres: the first in file order
+    assert not np.isin(tie["object"], np.arange(1, 24)).any()
+    co = am.aov(specs["coincident"], 1, am.CENTER, 0)
+    assert set(np.unique(co["object"])) <= {-1, 0, 2}
+    assert (am.aov(specs["tiny"], 3, am.CENTER, 0)["object"] == -1).all()
+    part = am.aov(specs["random"], 4, am.RANDOM, am.SEEDS[0])["coverage"]
+    assert ((part > 0) & (part < 1)).sum() > 20               # silhouettes: some samples hit, some miss
+    far = am.aov(specs["far"], 1, am.CENTER, 0)
+    assert (far["object"] >= 0).sum() > 5
+
+
+@pytest.mark.parametrize("name", ["inside", "nan_plane", "extreme"])
+def test_vectorised_sphere_quadratic_is_the_oracles(specs, name):
+    spec = specs[name]
+    o, d = am.camera_rays(spec, am.RANDOM, am.SEEDS[1], 2)
+    d = d.reshape(-1, 3)
+    hits = 0
+    for ob in spec.objects:
+        if ob["shape"] != "sphere":
+            continue
+        hit, t, n = am.sphere_hits(ob["center"], ob["radius"], o, d)
+        for k in range(d.shape[0]):
+            r = ref64.sphere_intersect(ob["center"], ob["radius"], tuple(o), tuple(d[k]))
+            assert (r is not None) == bool(hit[k]), (name, k)
+            if r is not None:
+                hits += 1
+                assert np.float64(r[0]).tobytes() == t[k].tobytes(), (name, k, r[0], t[k])
+                assert np.array(r[1], np.float64).tobytes() == n[k].tobytes(), (name, k)
+    assert hits > 50
+
+
+def test_keyed_draws_are_the_oracles():
+    """The key functions restated in aov_model against the oracle's keyed render: a one-object flat scene whose
+    coverage under random jitter depends on every jitter draw of every pixel."""
+    s = scenes.SceneSpec(width=24, height=16, camera=dict(scenes.DEFAULT_CAMERA), name="keys")
+    s.sphere((0.0, 1.0, -6.0), 2.5, scenes.phong((0.3, 0.3, 0.3), (0, 0, 0), 1.0, (0, 0, 0)))
+    for seed in (0, 1, 2 ** 63 + 12345):
+        m = am.aov(s, 5, am.RANDOM, seed)
+        cov = oracle_f32(am.flat_coverage(s, 5), am.RANDOM, seed)[:, :, 0]
+        assert same_bits(cov, m["coverage"])
+        assert ((cov > 0) & (cov < 1)).any()
+    assert 0.0 <= am.key_f64(am.key_child(am.key_pixel(1, 2, 3), 4), 0) < 1.0
+
+
+def test_aov_planner(tmp_path):
+    exe = str(tmp_path / "aov_plan_check")
+    cmd = [os.environ.get("CXX", "g++")] + CXXFLAGS + SAN + ["-o", exe, os.path.join(NATIVE, "aov_plan_check.cpp"),
+                                                            os.path.join(CSRC, "render_plan.cpp")]
+    cc = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    assert cc.returncode == 0, cc.stdout
+    run = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=300)
+    assert run.returncode == 0, run.stdout
+    assert "aov_plan_check ok" in run.stdout
+
+
+def test_entry_points_are_declared_and_exported():
+    names = lr.header_functions()
+    assert "rt_render_aov" in names and "rt_render_aov_device" in names
+    assert hasattr(lr.lib, "rt_render_aov") and hasattr(lr.lib, "rt_render_aov_device")
+    assert lr.RT_ABI_VERSION == 9 == lr.lib.rt_abi_version()
+    assert (lr.RT_AOV_DEPTH, lr.RT_AOV_NORMAL, lr.RT_AOV_ALBEDO, lr.RT_AOV_COVERAGE, lr.RT_AOV_OBJECT) == (1, 2, 4, 8, 16)
+    assert C.sizeof(lr.rt_aov_buffers) == 5 * C.sizeof(C.c_void_p)
+    # a null context is refused before anything is touched
+    o = lr.render_opts(8, 8)
+    b = lr.rt_aov_buffers()
+    assert lr.lib.rt_render_aov(None, C.byref(o), lr.RT_AOV_DEPTH, C.byref(b), None) == lr.RT_E_INVALID
+    assert lr.lib.rt_render_aov_device(None, C.byref(o), lr.RT_AOV_DEPTH, C.byref(b), None) == lr.RT_E_INVALID
+
+
+def test_without_a_device_there_is_no_context_to_render_with():
+    """rt_render_aov needs a context, and without a device rt_ctx_create answers RT_E_NODEVICE."""
+    h = C.c_void_p()
+    rc = lr.lib.rt_ctx_create(0, C.byref(h))
+    if lr.device_count() == 0:
+        assert rc == lr.RT_E_NODEVICE and not h.value
+    else:
+        assert rc == lr.RT_OK
+        lr.lib.rt_ctx_destroy(h)
