@@ -61,7 +61,9 @@
 extern "C" {
 #endif
 
-/* 9: first-hit feature buffers: enum rt_aov, rt_aov_buffers, rt_render_aov and rt_render_aov_device
+/* 10: rt_isect_check and rt_shade_check added (record-level diagnostics of the sphere and plane tests and
+ * of the shading arithmetic, DESIGN.md 4 "Primitive probes").  No struct, enum value or tuning key changed.
+ * 9: first-hit feature buffers: enum rt_aov, rt_aov_buffers, rt_render_aov and rt_render_aov_device
  * (depth, normal, albedo, coverage and object id of the camera rays' first hits).  Functions and types
  * added only: no struct, enum value or tuning key changed, RT_KF_COUNT is still 8.
  * 8: rt_cull_check and rt_cull_reach added (diagnostics of the conservative f32 culling and of the
@@ -85,7 +87,7 @@ extern "C" {
  * 4: rt_abi_version() added; RT_KF_TAIL (RT_KF_COUNT 8).  A caller checks
  * rt_abi_version() == RT_ABI_VERSION of the header it was built against before
  * passing any struct; any change of a struct, enum value or tuning key bumps it. */
-#define RT_ABI_VERSION 9
+#define RT_ABI_VERSION 10
 
 enum rt_status {
     RT_OK = 0,
@@ -476,6 +478,30 @@ int rt_sqrt_check(rt_ctx* ctx, const double* x, uint32_t n, double* fast, double
  * (tests/test_gpu_culling.py).  Synchronous. */
 int rt_cull_check(rt_ctx* ctx, uint32_t n, const double* rays, const float* boxes, const double* t, const int32_t* codes,
                   double reach, int32_t* out_i, float* out_f);
+/* Diagnostic (device): the exact f64 sphere and plane tests (shapes.rs:60-89, 100-112), computed by the
+ * functions the render kernels call, for n records.  Record i: records[16 i ..] = ray origin, ray direction,
+ * sphere centre, sphere radius, plane point, plane normal (f64; the radius is squared on the host as the scene
+ * upload squares it).  Outputs: out_i[3 i ..] = { hit of the branch-free sphere test (the form every LDS and
+ * BVH walk runs); hit of the branchy form (the binary16 walk of trees beyond LDS); hit of the plane test };
+ * out_d[15 i ..] = { t of the branch-free form; t of the branchy form; the plane's t as computed, whatever
+ * the verdict (NaN, +-inf, +-0 included); hit point o + d t and normal (shapes.rs:61,66) of the branch-free
+ * form's hit, 6 values; the same of the branchy form's }.  A sphere miss reports t 0 and a zero point and
+ * normal.  Tests compare with an operation-by-operation f64 model that is pinned to the oracle
+ * (tests/prim_model.py, tests/test_gpu_prims.py).  Synchronous. */
+int rt_isect_check(rt_ctx* ctx, uint32_t n, const double* records, int32_t* out_i, double* out_d);
+/* Diagnostic (device): the shading arithmetic of one hit, one material and one light (raytrace.rs:30-62,
+ * 123-163; scene.rs:122-138), computed by the functions the render kernels call, and the device's pow, sin
+ * and cos, for n records.  Record i: records[27 i ..] = hit point 3, shape normal 3 (as the intersection
+ * returned it: the probe orients it against the ray as the kernels do), incoming ray direction 3, diffuse 3,
+ * specular 3, exponent, ior, light location (point) or direction (directional) 3, light colour 3, the ray's
+ * significance, then three operands of their own: x and y of pow(x, y), x of sin(x) and cos(x);
+ * kinds[2 i ..] = { rt_material_kind (RT_MAT_PHONG or RT_MAT_FRESNEL), rt_light_kind (RT_LIGHT_POINT or
+ * RT_LIGHT_DIRECTIONAL) }.  Outputs: out_i[3 i ..] = { the light has a range; the diffuse flag; the specular
+ * flag (raytrace.rs:35-36 / 137-138) }; out_d[20 i ..] = { light direction 3; squared range; the Schlick factor
+ * of the material's ior whatever its kind; the factor f the flags used (1 for Phong); the mirror ray's origin
+ * and direction (raytrace.rs:60-62) 6; the half vector's clamped cosine c; p = pow(c, exponent); the colour one
+ * unshadowed light adds to black with both flags on 3; pow(x, y); sin(x); cos(x) }.  Synchronous. */
+int rt_shade_check(rt_ctx* ctx, uint32_t n, const double* records, const int32_t* kinds, int32_t* out_i, double* out_d);
 /* host only: the culling domain of a scene whose spheres' largest finite |centre +- radius| is extent,
  * 32 (1 + extent) rounded down to f32: rays, shade points and cameras whose f32-rounded coordinates lie
  * within it on every axis are culled through the padded boxes, the others test every sphere (DESIGN.md

@@ -130,6 +130,13 @@ hipError_t launch_sqrt_probe(const double* x, uint32_t n, double* fast, double* 
 // Diagnostic: the tree walks' f32 culling arithmetic on n (ray, box, t, code) records (rt_cull_check).
 hipError_t launch_cull_probe(uint32_t n, const double* rays, const float* boxes, const double* t, const int32_t* codes,
                              float reach, int32_t* out_i, float* out_f, hipStream_t s);
+// Diagnostic: sphere_t in both forms, plane_t, the hit point and hit_normal on n records of 16 doubles
+// (rt_isect_check; probes.hip has the layouts).
+hipError_t launch_isect_probe(uint32_t n, const double* in, int32_t* out_i, double* out_d, hipStream_t s);
+// Diagnostic: light_dir, fresnel_factor, shading_flags, reflect_ray, spec_power, add_light and the device's
+// pow / sin / cos on n records of 29 doubles and 2 ints (rt_shade_check).
+hipError_t launch_shade_probe(uint32_t n, const double* in_d, const int32_t* in_i, int32_t* out_i, double* out_d,
+                              hipStream_t s);
 
 // First-hit feature buffers (wf_aov.hip, rt_render_aov): device buffers of the tile, tile row-major; null: the
 // channel is not selected and costs nothing.  normal and albedo: 3 floats per pixel.

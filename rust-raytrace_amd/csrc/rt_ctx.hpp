@@ -193,6 +193,11 @@ struct rt_ctx {
 
 namespace rtamd {
 
+// What the scene upload derives on the host with the reference's own f64 operations, so that the
+// device reads the same bits (rt_scene_upload.cpp; the probes of rt_device.cpp form them the same way).
+inline double significance(const rt_color& c) { return c.r + c.g + c.b; }   // color.rs:637-639
+inline double sphere_rr(double radius) { return radius * radius; }          // shapes.rs:65, DevSphere::rr
+
 inline int fail(rt_ctx* c, int code, const std::string& msg) {
     if (c) c->err = msg;
     set_thread_error(msg);

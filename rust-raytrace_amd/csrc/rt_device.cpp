@@ -4,10 +4,40 @@
 #include <cstring>
 #include <new>
 #include <string>
+#include <vector>
 
 #include "rt_ctx.hpp"
 
 using namespace rtamd;
+
+namespace {
+
+// Upload n records of `in_d` doubles (and `in_i` ints, 0: none), run `launch` on the device copies, download
+// the records' `out_i` ints and `out_d` doubles.  One allocation, the doubles first (8-byte aligned).
+template <class Launch>
+int run_record_probe(rt_ctx* c, uint32_t n, const double* in_d, size_t n_in_d, const int32_t* in_i, size_t n_in_i,
+                     int32_t* out_i, size_t n_out_i, double* out_d, size_t n_out_d, Launch&& launch) {
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t N = n;
+    const size_t o_od = 8 * n_in_d * N, o_ii = o_od + 8 * n_out_d * N, o_oi = o_ii + 4 * n_in_i * N;
+    uint8_t* d = nullptr;
+    HIP_TRY(c, hipMalloc(&d, o_oi + 4 * n_out_i * N));
+    auto body = [&]() -> int {
+        HIP_TRY(c, hipMemcpyAsync(d, in_d, o_od, hipMemcpyHostToDevice, c->stream));
+        if (n_in_i) HIP_TRY(c, hipMemcpyAsync(d + o_ii, in_i, 4 * n_in_i * N, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, launch(reinterpret_cast<const double*>(d), reinterpret_cast<const int32_t*>(d + o_ii),
+                          reinterpret_cast<int32_t*>(d + o_oi), reinterpret_cast<double*>(d + o_od)));
+        HIP_TRY(c, hipMemcpyAsync(out_i, d + o_oi, 4 * n_out_i * N, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(out_d, d + o_od, 8 * n_out_d * N, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        return RT_OK;
+    };
+    const int rc = body();
+    (void)hipFree(d);
+    return rc;
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -143,6 +173,41 @@ int rt_cull_check(rt_ctx* c, uint32_t n, const double* rays, const float* boxes,
         const int rc = body();
         (void)hipFree(d);
         return rc;
+    });
+}
+
+int rt_isect_check(rt_ctx* c, uint32_t n, const double* records, int32_t* out_i, double* out_d) {
+    if (!c || (n && (!records || !out_i || !out_d))) return RT_E_INVALID;
+    if (n == 0) return RT_OK;
+    return guarded(c, [&] {
+        // the device's sphere carries rr = radius * radius, formed as the upload forms it
+        std::vector<double> in(records, records + 16 * static_cast<size_t>(n));
+        for (size_t i = 0; i < n; ++i) in[16 * i + 9] = sphere_rr(in[16 * i + 9]);
+        return run_record_probe(c, n, in.data(), 16, nullptr, 0, out_i, 3, out_d, 15,
+                                [&](const double* di, const int32_t*, int32_t* oi, double* od) {
+                                    return launch_isect_probe(n, di, oi, od, c->stream);
+                                });
+    });
+}
+
+int rt_shade_check(rt_ctx* c, uint32_t n, const double* records, const int32_t* kinds, int32_t* out_i, double* out_d) {
+    if (!c || (n && (!records || !kinds || !out_i || !out_d))) return RT_E_INVALID;
+    if (n == 0) return RT_OK;
+    return guarded(c, [&] {
+        // 27 -> 29 doubles: the material's kd_sig and ks_sig (the upload's significance()) go in after ks
+        std::vector<double> in(29 * static_cast<size_t>(n));
+        for (size_t i = 0; i < n; ++i) {
+            const double* q = records + 27 * i;
+            double* o = in.data() + 29 * i;
+            for (int k = 0; k < 15; ++k) o[k] = q[k];
+            o[15] = significance(rt_color{q[9], q[10], q[11]});
+            o[16] = significance(rt_color{q[12], q[13], q[14]});
+            for (int k = 15; k < 27; ++k) o[k + 2] = q[k];
+        }
+        return run_record_probe(c, n, in.data(), 29, kinds, 2, out_i, 3, out_d, 20,
+                                [&](const double* di, const int32_t* ii, int32_t* oi, double* od) {
+                                    return launch_shade_probe(n, di, ii, oi, od, c->stream);
+                                });
     });
 }
 

@@ -19,8 +19,6 @@ static_assert(kMatPhong == RT_MAT_PHONG && kMatFresnel == RT_MAT_FRESNEL && kMat
               "DevMaterial::kind mirrors rt_material_kind");
 static_assert(kLightArea == RT_LIGHT_AREA, "DevLight::kind mirrors rt_light_kind");
 
-double significance(const rt_color& c) { return c.r + c.g + c.b; }   // color.rs:637-639
-
 }  // namespace
 
 extern "C" {
@@ -38,7 +36,7 @@ int rt_light_grid_candidates(const rt_scene* s, int light, int resolution, const
         for (size_t i = 0; i < s->objects.size(); ++i) {
             const rt_object& o = s->objects[i];
             if (o.shape != RT_SHAPE_SPHERE) continue;
-            spheres.push_back(DevSphere{o.geom[0], o.geom[1], o.geom[2], o.geom[3] * o.geom[3]});
+            spheres.push_back(DevSphere{o.geom[0], o.geom[1], o.geom[2], sphere_rr(o.geom[3])});
             srad.push_back(o.geom[3]);
             obj.push_back(static_cast<int32_t>(i));
             const double r = std::fabs(o.geom[3]);
@@ -101,7 +99,7 @@ int rt_view_grid_candidates(const rt_scene* s, int resolution, const double* dir
         for (size_t i = 0; i < s->objects.size(); ++i) {
             const rt_object& o = s->objects[i];
             if (o.shape != RT_SHAPE_SPHERE) continue;
-            spheres.push_back(DevSphere{o.geom[0], o.geom[1], o.geom[2], o.geom[3] * o.geom[3]});
+            spheres.push_back(DevSphere{o.geom[0], o.geom[1], o.geom[2], sphere_rr(o.geom[3])});
             srad.push_back(o.geom[3]);
             obj.push_back(static_cast<int32_t>(i));
             const double r = std::fabs(o.geom[3]);
@@ -238,7 +236,7 @@ static int scene_upload(rt_ctx* c, const rt_scene* s) {
             return fail(c, RT_E_INVALID, "object " + std::to_string(i) + ": bad material kind");
         needs_path |= o.material == RT_MAT_INDIRECT_PHONG || o.material == RT_MAT_TRANSPARENT;
         if (o.shape == RT_SHAPE_SPHERE) {
-            spheres.push_back(DevSphere{o.geom[0], o.geom[1], o.geom[2], o.geom[3] * o.geom[3]});
+            spheres.push_back(DevSphere{o.geom[0], o.geom[1], o.geom[2], sphere_rr(o.geom[3])});
             sphere_obj.push_back(static_cast<int32_t>(i));
             sx.push_back(o.geom[0]); sy.push_back(o.geom[1]); sz.push_back(o.geom[2]); srad.push_back(o.geom[3]);
         } else if (o.shape == RT_SHAPE_PLANE) {

@@ -6,7 +6,8 @@
 // reference's order, compiled with -ffp-contract=off (no FMA fusion; Rust never
 // fuses).  f64 add/mul/div/sqrt are IEEE correctly rounded on gfx950, so the
 // only possible difference from the CPU is pow() (raytrace.rs:55): OCML vs
-// glibc, <= 1 ulp (measured: bit-identical on every parity scene so far).
+// glibc, <= 1 ulp (measured through rt_shade_check, tests/test_gpu_prims.py: at most one
+// representable value from correctly rounded; bit-identical on every parity scene so far).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -1312,6 +1313,22 @@ __device__ __forceinline__ Shading shading_flags(const DevMaterial& m, double si
     return s;
 }
 
+// The specular term's power (raytrace.rs:55): c = clamp_zero(n . normalize(l - d)), the half
+// vector's cosine, and pow(c, exponent).  add_light's own lines, as a function of their own
+// so that rt_shade_check (probes.hip) reports the c and p that add_light uses.
+__device__ __forceinline__ double spec_power(const DevMaterial& m, double lx, double ly, double lz, double nx, double ny,
+                                             double nz, double dx, double dy, double dz, double& c) {
+    const double hx = lx - dx, hy = ly - dy, hz = lz - dz;
+#if RT_DIVK
+    const DivK hl = div_k(sqrt_win(hx * hx + hy * hy + hz * hz));
+    c = clamp_zero(nx * div_by(hx, hl) + ny * div_by(hy, hl) + nz * div_by(hz, hl));
+#else
+    const double hl = sqrt(hx * hx + hy * hy + hz * hz);
+    c = clamp_zero(nx * (hx / hl) + ny * (hy / hl) + nz * (hz / hl));
+#endif
+    return pow(c, m.exponent);
+}
+
 // The diffuse and specular terms of one unshadowed light (raytrace.rs:51-56,
 // Fresnel: 151-156, where the specular term is ((ks * lc) * f) * pow).
 __device__ __forceinline__ void add_light(Col& res, const DevMaterial& m, const DevLight& L, bool diffuse, bool specular,
@@ -1324,15 +1341,8 @@ __device__ __forceinline__ void add_light(Col& res, const DevMaterial& m, const 
         res.b = res.b + ((m.kd[2] * L.color[2]) * s) * kFrac1Pi;
     }
     if (specular) {
-        const double hx = lx - dx, hy = ly - dy, hz = lz - dz;
-#if RT_DIVK
-        const DivK hl = div_k(sqrt_win(hx * hx + hy * hy + hz * hz));
-        const double c = clamp_zero(nx * div_by(hx, hl) + ny * div_by(hy, hl) + nz * div_by(hz, hl));
-#else
-        const double hl = sqrt(hx * hx + hy * hy + hz * hz);
-        const double c = clamp_zero(nx * (hx / hl) + ny * (hy / hl) + nz * (hz / hl));
-#endif
-        const double p = pow(c, m.exponent);
+        double c;
+        const double p = spec_power(m, lx, ly, lz, nx, ny, nz, dx, dy, dz, c);
         res.r = res.r + ((m.ks[0] * L.color[0]) * f) * p;
         res.g = res.g + ((m.ks[1] * L.color[1]) * f) * p;
         res.b = res.b + ((m.ks[2] * L.color[2]) * f) * p;

@@ -20,7 +20,7 @@ PKG_DIR = os.path.dirname(_HERE)
 LIB_PATH = os.environ.get("RT_LIBRTAMD") or os.path.join(PKG_DIR, "librtamd.so")
 HEADER_PATH = os.path.join(os.path.dirname(PKG_DIR), "include", "raytrace_amd.h")
 
-RT_ABI_VERSION = 9               # include/raytrace_amd.h
+RT_ABI_VERSION = 10              # include/raytrace_amd.h
 RT_OK = 0
 RT_E_INVALID, RT_E_NODEVICE, RT_E_HIP, RT_E_NOMEM = -1, -2, -3, -4
 RT_E_UNSUPPORTED, RT_E_PARSE, RT_E_NOSCENE, RT_E_IO = -5, -6, -7, -8
@@ -158,6 +158,8 @@ def _load():
         "rt_sqrt_check": (C.c_int, [C.c_void_p, P(C.c_double), C.c_uint32, P(C.c_double), P(C.c_double)]),
         "rt_cull_check": (C.c_int, [C.c_void_p, C.c_uint32, P(C.c_double), P(C.c_float), P(C.c_double), P(C.c_int32),
                                     C.c_double, P(C.c_int32), P(C.c_float)]),
+        "rt_isect_check": (C.c_int, [C.c_void_p, C.c_uint32, P(C.c_double), P(C.c_int32), P(C.c_double)]),
+        "rt_shade_check": (C.c_int, [C.c_void_p, C.c_uint32, P(C.c_double), P(C.c_int32), P(C.c_int32), P(C.c_double)]),
         "rt_cull_reach": (C.c_double, [C.c_double]),
         "rt_ctx_set_tuning": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int64]),
         "rt_ctx_get_tuning": (C.c_int, [C.c_void_p, C.c_char_p, P(C.c_int64)]),
@@ -568,6 +570,43 @@ class Context:
                self._h)
         return {"te": oi[:, 0], "hit": oi[:, 1] != 0, "hit_nf": oi[:, 2] != 0, "node16": oi[:, 3], "node18": oi[:, 4],
                 "tlim": of[:, 0], "tnear": of[:, 1], "tnear_nf": of[:, 2], "t16": of[:, 3], "t18": of[:, 4]}
+
+    def isect_check(self, rays, spheres, planes):
+        """Diagnostic (rt_isect_check): the exact sphere and plane tests on n records: rays [n, 6] (origin,
+        direction), spheres [n, 4] (centre, radius), planes [n, 6] (point, normal), float64.  Returns a dict of
+        arrays: hit_bf, t_bf, pt_bf [n, 3], n_bf [n, 3] (the branch-free sphere test), hit_br, t_br, pt_br, n_br
+        (the branchy form), hit_pl, t_pl (the plane test; t as computed whatever the verdict)."""
+        rec = np.ascontiguousarray(np.concatenate([np.asarray(rays, np.float64), np.asarray(spheres, np.float64),
+                                                   np.asarray(planes, np.float64)], axis=1))
+        n = rec.shape[0]
+        assert rec.shape == (n, 16)
+        oi = np.empty((n, 3), np.int32)
+        od = np.empty((n, 15), np.float64)
+        PD, PI = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+        _check(lib.rt_isect_check(self._h, n, rec.ctypes.data_as(PD), oi.ctypes.data_as(PI), od.ctypes.data_as(PD)),
+               self._h)
+        return {"hit_bf": oi[:, 0] != 0, "hit_br": oi[:, 1] != 0, "hit_pl": oi[:, 2] != 0, "t_bf": od[:, 0],
+                "t_br": od[:, 1], "t_pl": od[:, 2], "pt_bf": od[:, 3:6], "n_bf": od[:, 6:9], "pt_br": od[:, 9:12],
+                "n_br": od[:, 12:15]}
+
+    def shade_check(self, records, kinds):
+        """Diagnostic (rt_shade_check): the shading arithmetic and the device's pow / sin / cos on n records:
+        records [n, 27] float64 (point 3, shape normal 3, ray direction 3, kd 3, ks 3, exponent, ior, light v 3,
+        light colour 3, significance, pow x, pow y, trig x), kinds [n, 2] int32 (material kind, light kind).
+        Returns a dict of arrays: ldir [n, 3], r2, has_range, fresnel, f, diffuse, specular, refl [n, 6] (the
+        mirror ray's origin and direction), c, p, col [n, 3], pow, sin, cos."""
+        rec = np.ascontiguousarray(records, dtype=np.float64)
+        kinds = np.ascontiguousarray(kinds, dtype=np.int32)
+        n = rec.shape[0]
+        assert rec.shape == (n, 27) and kinds.shape == (n, 2)
+        oi = np.empty((n, 3), np.int32)
+        od = np.empty((n, 20), np.float64)
+        PD, PI = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+        _check(lib.rt_shade_check(self._h, n, rec.ctypes.data_as(PD), kinds.ctypes.data_as(PI), oi.ctypes.data_as(PI),
+                                  od.ctypes.data_as(PD)), self._h)
+        return {"ldir": od[:, 0:3], "r2": od[:, 3], "fresnel": od[:, 4], "f": od[:, 5], "refl": od[:, 6:12],
+                "c": od[:, 12], "p": od[:, 13], "col": od[:, 14:17], "pow": od[:, 17], "sin": od[:, 18],
+                "cos": od[:, 19], "has_range": oi[:, 0] != 0, "diffuse": oi[:, 1] != 0, "specular": oi[:, 2] != 0}
 
     def accumulator(self, opts):
         """rt_accum_create: a progressive render of opts' tile (main.rs:47-56 split over calls), bound to

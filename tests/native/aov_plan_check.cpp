@@ -49,7 +49,7 @@ static SceneFacts big_scene() {       // 100k spheres: nothing fits LDS
 static void source_cases() {
     static_assert(RT_AOV_DEPTH == 1 && RT_AOV_NORMAL == 2 && RT_AOV_ALBEDO == 4 && RT_AOV_COVERAGE == 8 && RT_AOV_OBJECT == 16,
                   "the values the header documents");
-    static_assert(RT_ABI_VERSION == 9 && RT_KF_COUNT == 8, "ABI 9 adds functions and types only");
+    static_assert(RT_ABI_VERSION == 10 && RT_KF_COUNT == 8, "ABI 9 adds functions and types only");
     // the camera's view grid where the scene has one: spheres in LDS when the list fits, else through L2
     SceneFacts f = small_scene();
     f.has_cgrid = true;

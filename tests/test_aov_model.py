@@ -146,7 +146,7 @@ def test_entry_points_are_declared_and_exported():
     names = lr.header_functions()
     assert "rt_render_aov" in names and "rt_render_aov_device" in names
     assert hasattr(lr.lib, "rt_render_aov") and hasattr(lr.lib, "rt_render_aov_device")
-    assert lr.RT_ABI_VERSION == 9 == lr.lib.rt_abi_version()
+    assert lr.RT_ABI_VERSION == 10 == lr.lib.rt_abi_version()
     assert (lr.RT_AOV_DEPTH, lr.RT_AOV_NORMAL, lr.RT_AOV_ALBEDO, lr.RT_AOV_COVERAGE, lr.RT_AOV_OBJECT) == (1, 2, 4, 8, 16)
     assert C.sizeof(lr.rt_aov_buffers) == 5 * C.sizeof(C.c_void_p)
     # a null context is refused before anything is touched
