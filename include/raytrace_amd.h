@@ -25,6 +25,9 @@
  *                         main.rs:39-56 with `raytrace(..)` replaced by what Scene::intersect (scene.rs:247-249)
  *                         answers for the camera ray: Hit.t, the shape's normal (shapes.rs:72, 79, 108) and the
  *                         hit object; no shading
+ *   rt_query_nearest / rt_query_occluded (and their _device variants)
+ *                         scene.rs:247-249 Scene::intersect and raytrace.rs:43-50 (the shadow test) for rays the
+ *                         caller supplies
  *   rt_scene_set_skybox   scene.rs:174-188       SkyboxBackground { px, nx, py, ny, pz, nz }
  *   rt_texture_load       texture.rs:34-37       Texture::load (BMP and binary PPM here; the image crate decodes more)
  *   rt_to_srgb            color.rs:593-600       fn to_srgb (used by Color::write_bgr, color.rs:628-632)
@@ -63,6 +66,9 @@ extern "C" {
 
 /* 10: rt_isect_check and rt_shade_check added (record-level diagnostics of the sphere and plane tests and
  * of the shading arithmetic, DESIGN.md 4 "Primitive probes").  No struct, enum value or tuning key changed.
+ * Still 10: the ray queries (enum rt_hit_channel, rt_hit_buffers, rt_query_nearest / rt_query_occluded and their
+ * device variants) add functions, one enum and one struct, and alter nothing a caller built against ABI 10 passes
+ * or reads; RT_KF_COUNT is still 8.  A caller that needs them looks the symbols up.
  * 9: first-hit feature buffers: enum rt_aov, rt_aov_buffers, rt_render_aov and rt_render_aov_device
  * (depth, normal, albedo, coverage and object id of the camera rays' first hits).  Functions and types
  * added only: no struct, enum value or tuning key changed, RT_KF_COUNT is still 8.
@@ -385,6 +391,69 @@ typedef struct { float* depth; float* normal; float* albedo; float* coverage; in
 int rt_render_aov(rt_ctx* ctx, const rt_render_opts* opts, uint32_t channels, const rt_aov_buffers* host, rt_stats* stats);
 /* Asynchronous on `stream` (NULL: the context's own), into caller-owned DEVICE buffers. */
 int rt_render_aov_device(rt_ctx* ctx, const rt_render_opts* opts, uint32_t channels, const rt_aov_buffers* dev, void* stream);
+/* ---- ray queries: nearest hit and occlusion for caller-supplied rays ----
+ * Scene::intersect (scene.rs:247-249) and the shadow test of raytrace.rs:43-50 for rays the caller builds: a baking
+ * pass, a line-of-sight test, a picking ray, rays made in tensors.  No shading, no recursion, no averaging.
+ *   rays[6 i ..] = origin x, y, z then direction x, y, z of ray i (f64): the [n, 6] layout of rt_cull_check and
+ *   rt_isect_check.  The direction is used as given, not normalised (Ray in shapes.rs does not normalise it either):
+ *   t is in units of the direction's length, and scaling a direction by 2^k scales every t by 2^-k exactly.
+ * Nearest hit: h = Scene::intersect(ray): the smallest t, the first object in file order on a tie, and a NaN t (only
+ * a plane's 0/0 gives one) beats everything (scene.rs:223-249).
+ *   output            hit                                                                   miss
+ *   t[i]              h.t                                                                   +inf
+ *   object[i]         the object id (file order, what Hit::obj holds)                       -1
+ *   normal[3 i ..]    the shape's normal as the intersection returns it: sphere             0.0, 0.0, 0.0
+ *                     normalize(ray.cast(t) - centre) (shapes.rs:72, 79), plane as in the
+ *                     file, not normalised (shapes.rs:108)
+ *   All f64, no rounding.  The normal is NOT oriented against the ray; a caller who wants the orientation of
+ *   rt_render_aov's normal applies raytrace.rs:38: negate it when dot(normal, ray.direction) > 0.0.
+ *   channels: a non-empty mask of rt_hit_channel; only the selected buffers are read from the struct and written.
+ * Occlusion: raytrace.rs:43-50 verbatim.  occluded[i] = 1 when Scene::intersect(ray) is Some(h) and (r2 is NULL or
+ *   h.t * h.t < r2[i]), else 0.  r2 NULL is the directional light's rule (scene.rs:131-139: no range), r2 the point
+ *   light's with the caller's squared range (scene.rs:125).  A plane's NaN t under a range is therefore not occluded
+ *   (NaN < r2 is false) and without a range it is.  The shadow ray raytrace.rs:43 itself issues from a hit point pt
+ *   towards a light direction ldir is origin = pt + ldir * 1e-5, direction = ldir.
+ * Domain of a ray: six finite components; |origin| <= 1e30 on every axis; the direction's largest component magnitude
+ *   in [2^-256, 2^256]; r2[i] not NaN and >= 0 (+inf allowed); and of the scene, for the queries: the spheres' extent
+ *   (the largest |centre +- radius|, rt_cull_reach's argument) <= 1e30 and every radius >= 1e-60.  Inside it the
+ *   answers are the reference's, bit for bit.  The exact tests are the reference's f64 operations in its order whatever
+ *   the magnitudes, but the tree sources cull with f32 boxes, and a box holds every hit the exact quadratic can report
+ *   only while the quadratic's intermediates keep their relative precision: a = d.d, b*b, 4a*c and the discriminant
+ *   neither overflow nor lose bits to underflow ("BVH exactness" item 1).  A wider bound such as 2^+-500
+ *   breaks that: with direction (2^500, 0, 0) from the coordinate origin, b*b overflows to +inf for a sphere of radius
+ *   2500 centred 3000 BEHIND the origin, the reference reports a hit at t = +inf (shapes.rs:65-79), the brute sources
+ *   do as well, and every tree source culls the box and reports a miss.  With 2^+-256, |origin| and extent <= 2^100:
+ *   a <= 2^514, |b| <= 2^360, b*b and 4a*c <= 2^722; a >= 2^-512, and b*b or 4a*c can fall below 2^-1022 only for
+ *   features below 2^-200 (hence the radius bound).  Within that the culling runs on the direction scaled by a power of
+ *   two whenever its largest component leaves [2^-20, 2^20] (every t limit scaled alike), and an origin beyond the
+ *   scene's culling domain (rt_cull_reach) is not culled at all: it tests every sphere; 1e30 keeps the origin's f32
+ *   image finite.  Outside the domain the values are unspecified (and may differ between tuning src values), but
+ *   nothing is read or written out of bounds.
+ * flags: RT_TIME_KERNELS alone (the launch is counted under RT_KF_NEAREST, an occlusion query's under
+ *   RT_KF_OCCLUSION); any other bit -> RT_E_INVALID.
+ * A query is a render of the context, as an AOV render is: ordered on the device after the previous render;
+ *   afterwards rt_ctx_stats reports rays = traced_rays = n, shadow_rays 0 (nearest) or n (occlusion), pixels 0,
+ *   chunks 0 and the work counters 0.  n = 0 is a valid render that launches nothing and touches no buffer (no
+ *   pointer is looked at).  A query neither needs nor frees the wavefront working set, an rt_accum or what
+ *   rt_ctx_reserve prepared.
+ * Refusals, each no render (the statistics stay the previous render's): RT_E_INVALID for unknown flag bits, channels
+ *   0 or with unknown bits, and with n > 0 a NULL rays / occluded / struct, a selected channel whose pointer is NULL,
+ *   and in the device variants a d_rays that is not 16-byte aligned (the kernel reads a ray as three 16-byte loads;
+ *   the host variants stage the rays, so any pointer is accepted there); RT_E_NOSCENE: no scene uploaded; RT_E_NOMEM:
+ *   the host variant's device buffers do not fit.  There is no RT_E_UNSUPPORTED case: only geometry is read, so every
+ *   scene class, camera and background is served. */
+enum rt_hit_channel { RT_HIT_T = 1, RT_HIT_OBJECT = 2, RT_HIT_NORMAL = 4 };
+typedef struct { double* t; int32_t* object; double* normal; } rt_hit_buffers;
+/* Synchronous, caller-owned HOST buffers (staged through device buffers the call allocates and frees). */
+int rt_query_nearest(rt_ctx* ctx, const double* rays, uint32_t n, uint32_t channels, const rt_hit_buffers* host,
+                     uint32_t flags, rt_stats* stats);
+int rt_query_occluded(rt_ctx* ctx, const double* rays, const double* r2, uint32_t n, uint8_t* occluded, uint32_t flags,
+                      rt_stats* stats);
+/* Asynchronous on `stream` (NULL: the context's own), caller-owned DEVICE buffers. */
+int rt_query_nearest_device(rt_ctx* ctx, const double* d_rays, uint32_t n, uint32_t channels, const rt_hit_buffers* dev,
+                            uint32_t flags, void* stream);
+int rt_query_occluded_device(rt_ctx* ctx, const double* d_rays, const double* d_r2, uint32_t n, uint8_t* d_occluded,
+                             uint32_t flags, void* stream);
 /* ---- progressive rendering (main.rs:47-56 split over calls) ----
  * The reference's pixel is `res = BLACK; for _ in 0..antialias { res = res + raytrace(..) }; res / antialias`
  * (main.rs:47-56).  An rt_accum keeps `res` of every pixel of one tile on the device between calls: f64
@@ -516,8 +585,9 @@ int rt_ctx_generation_counts(rt_ctx* ctx, uint32_t* queue, uint32_t* shaded, int
  * count; then resets.  Synchronises with the last timed launch.  Families:
  * rt_kernel_family.  Renders split over several chunk streams are not timed. */
 enum rt_kernel_family {
-    RT_KF_NEAREST = 0,      /* wf_nearest, generations >= 1 */
-    RT_KF_OCCLUSION = 1,    /* wf_occlusion: every (record, light) pair of a generation */
+    RT_KF_NEAREST = 0,      /* wf_nearest, generations >= 1; query_nearest of an RT_TIME_KERNELS rt_query_nearest */
+    RT_KF_OCCLUSION = 1,    /* wf_occlusion: every (record, light) pair of a generation; query_occluded of an
+                               RT_TIME_KERNELS rt_query_occluded */
     RT_KF_SHADE = 2,        /* wf_shade */
     RT_KF_FOLD = 3,         /* wf_fold */
     RT_KF_TALLY = 4,        /* wf_tally */

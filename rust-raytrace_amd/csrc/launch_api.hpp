@@ -1,6 +1,6 @@
 // Host-side launchers of the kernels in the .hip translation units (called by rt_render.cpp and
 // rt_device.cpp): trace_mega.hip, the wavefront schedule's wf_sequence.hip and, behind it, its
-// kernel families (wf_launch.hpp), wf_output.hip, wf_aov.hip, probes.hip and path_kernel.hip.
+// kernel families (wf_launch.hpp), wf_output.hip, wf_aov.hip, wf_query.hip, probes.hip and path_kernel.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -152,6 +152,23 @@ struct AovOut {
 // workgroup adds its pixels * fp.spp to a shard of fp.counters (the rays of the render).
 hipError_t launch_aov(const DevScene& sc, const FrameParams& fp, const AovOut& out, int src, uint32_t workgroups,
                       hipStream_t s);
+
+// Ray queries (wf_query.hip, rt_query_nearest / rt_query_occluded): n caller-supplied rays, 6 doubles each (origin,
+// direction) from a 16-byte aligned device address.  Outputs per ray; null: the channel is not selected and costs
+// nothing.  normal: 3 doubles per ray.
+struct QueryOut {
+    double* t;
+    int32_t* object;
+    double* normal;
+};
+// query_nearest / query_occluded from sphere source src (render_plan.hpp, plan_query_source / plan_query_occ_source;
+// an unknown one: hipErrorInvalidValue), `workgroups` workgroups of kWfThreads striding over the rays; each workgroup
+// adds its rays to a shard of counters (FrameParams::counters: rays, and for occlusion shadow rays too).  r2 null: no
+// range (the directional light's rule).  n > 0.
+hipError_t launch_query_nearest(const DevScene& sc, unsigned long long* counters, const double* rays, uint32_t n,
+                                const QueryOut& out, int src, uint32_t workgroups, hipStream_t s);
+hipError_t launch_query_occluded(const DevScene& sc, unsigned long long* counters, const double* rays, const double* r2,
+                                 uint32_t n, uint8_t* occluded, int src, uint32_t workgroups, hipStream_t s);
 
 // The general path (path_kernel.hip): every material / light / camera class,
 // keyed random draws, one work-item per pixel over the HBM recursion stack.

@@ -199,6 +199,87 @@ uint32_t plan_aov_workgroups(uint64_t npix, int n_cu) {
     return static_cast<uint32_t>(std::max<uint64_t>(1, std::min<uint64_t>(need, 2ull * static_cast<uint64_t>(std::max(n_cu, 1)))));
 }
 
+QuerySource plan_query_source(const SceneFacts& sf, const int64_t* tune) {
+    SceneFacts f = sf;
+    f.has_cgrid = false;                          // the camera's grid is no structure for a foreign origin
+    const AovSource a = plan_aov_source(f, tune);
+    return QuerySource{a.src, a.pfx2};
+}
+
+QuerySource plan_query_occ_source(const SceneFacts& sf, const int64_t* tune) {
+    QuerySource q;
+    int64_t t[kTuneCount];
+    for (int i = 0; i < kTuneCount; ++i) t[i] = tune[i];
+    t[kTuneQTree] = 0;
+    t[kTuneSrc] = t[kTuneSrcOcc] = -1;
+    const SourcePair sp = plan_sources(sf, t, RT_ALGO_WAVEFRONT);
+    q.pfx2 = sp.pfx2;
+    const size_t sph_bytes = static_cast<size_t>(sf.n_spheres) * (sizeof(DevSphere) + sizeof(int32_t));
+    const bool fit2 = static_cast<size_t>(sf.n_bvh) * sizeof(DevBvhNode) + sph_bytes <= kLdsBudget;
+    const bool fit4 = static_cast<size_t>(sf.n_bvh4) * kBvh4Planes * sizeof(DevBvh4Plane) + sph_bytes <= kLdsBudget;
+    const int brute = static_cast<size_t>(sf.n_spheres) * sizeof(DevSphere) <= 64 * 1024 ? 1 : 0;
+    const bool tree = sf.n_bvh > 0;
+    const bool wide = tree && !sf.deep_bvh4;     // the 4-wide stack could overflow otherwise
+    q.src = tree ? sp.src_occ : brute;
+    int64_t forced = tune[kTuneSrcOcc];
+    if (forced == 14 || forced == 15) forced = fit4 ? 10 : 11;
+    switch (forced) {
+    case 0: q.src = 0; break;
+    case 1: q.src = brute; break;
+    case 2: case 8: if (tree) q.src = static_cast<int>(forced); break;
+    case 7: if (tree && fit2) q.src = 7; break;
+    case 10: if (wide && fit4) q.src = 10; break;
+    case 11: if (wide) q.src = 11; break;
+    default: break;
+    }
+    return q;
+}
+
+int plan_query_args(const QueryArgs& a, const char** err) {
+    if (a.flags & ~kQueryFlags) {
+        *err = "ray query: flags take RT_TIME_KERNELS only";
+        return RT_E_INVALID;
+    }
+    if (!a.occlusion) {
+        if (a.channels == 0) {
+            *err = "rt_query_nearest: no channel selected";
+            return RT_E_INVALID;
+        }
+        if (a.channels & ~kHitAll) {
+            *err = "rt_query_nearest: unknown channel bits";
+            return RT_E_INVALID;
+        }
+    }
+    if (a.n == 0) return RT_OK;
+    if (!a.rays) {
+        *err = "ray query: rays is NULL";
+        return RT_E_INVALID;
+    }
+    if (a.device && (reinterpret_cast<uintptr_t>(a.rays) & 15u)) {
+        *err = "ray query: the device rays are not 16-byte aligned (a ray is read as three 16-byte loads)";
+        return RT_E_INVALID;
+    }
+    if (a.occlusion) {
+        if (!a.occluded) {
+            *err = "rt_query_occluded: occluded is NULL";
+            return RT_E_INVALID;
+        }
+        return RT_OK;
+    }
+    if (!a.has_bufs) {
+        *err = "rt_query_nearest: the buffer struct is NULL";
+        return RT_E_INVALID;
+    }
+    for (int i = 0; i < 3; ++i)
+        if (((a.channels >> i) & 1u) && !a.ptrs[i]) {
+            *err = "rt_query_nearest: a selected channel's buffer is NULL";
+            return RT_E_INVALID;
+        }
+    return RT_OK;
+}
+
+uint32_t plan_query_workgroups(uint64_t n, int n_cu) { return plan_aov_workgroups(n, n_cu); }
+
 StreamShape plan_streams(const SceneFacts& sf, const int64_t* tune, int mode, int src, uint32_t max_depth) {
     StreamShape s;
     // tuning "split" 0: every kernel on one in-order stream (A/B measurement);

@@ -107,6 +107,50 @@ int plan_aov_args(uint32_t channels, const void* const ptrs[5], const char** err
 // Workgroups of the launch: one 1024-thread workgroup per 1024 pixels, at most two per CU (all resident).
 uint32_t plan_aov_workgroups(uint64_t npix, int n_cu);
 
+// ---- ray queries (rt_query_nearest / rt_query_occluded) ---------------------------------------
+// The sphere source of query_nearest (wf_query.hip), one caller-supplied ray per work-item: what plan_aov_source
+// gives with the camera's view grid left out (the grid is built around the camera's position and says nothing about
+// a foreign origin): tuning cam does not enter, tuning src forces 0, 1, 2, 5, 6, 7, 8, 9 as there, and the quantised
+// tree (25, 26, tuning qtree) takes what the scene would get without it.  pfx2: DevScene::pfx2 for the prefix sources.
+struct QuerySource {
+    int src = 0;
+    int32_t pfx2 = 0;
+};
+QuerySource plan_query_source(const SceneFacts& sf, const int64_t* tune);
+// The sphere source of query_occluded: the shadow source plan_sources pairs for RT_ALGO_WAVEFRONT without any forcing
+// (the 4-wide tree whole in LDS, 10, or through L2, 11; a tree the 4-wide stack could overflow: the binary tree, 7 in
+// LDS or 2); a scene without a spheres' tree: brute force from LDS (1) when the list fits 64 KB, else through the
+// caches (0).  The light grids (14, 15) belong to the scene's own lights and say nothing about a caller's ray: they
+// are never chosen.  Tuning src_occ forces 0, 1 (0 when the list does not fit), 2, 7, 8, 10, 11 where the scene has
+// that structure and it fits; 14 / 15 ask for the tree they fall back to (10 in LDS, 11 beyond); any other value, or
+// one that is not available, takes the automatic choice.  Tuning src does not enter.
+QuerySource plan_query_occ_source(const SceneFacts& sf, const int64_t* tune);
+// The sphere sources query_nearest / query_occluded are instantiated for: one list each, from which both the
+// launchers' cases (wf_query.hip) and the planner's check below are made, so that they cannot drift apart.
+#define RT_QUERY_NEAREST_SRCS(X) X(0) X(1) X(2) X(5) X(6) X(7) X(8) X(9)
+#define RT_QUERY_OCC_SRCS(X) X(0) X(1) X(2) X(7) X(8) X(10) X(11)
+#define RT_QUERY_SRC_IS(s) || src == (s)
+constexpr bool query_source_known(int src) { return false RT_QUERY_NEAREST_SRCS(RT_QUERY_SRC_IS); }
+constexpr bool query_occ_source_known(int src) { return false RT_QUERY_OCC_SRCS(RT_QUERY_SRC_IS); }
+// The call's argument checks that need no device.  What every call gets: flags RT_TIME_KERNELS alone.  nearest:
+// channels a non-empty mask of rt_hit_channel.  With n > 0: rays set, and (device) 16-byte aligned; nearest: bufs (the
+// caller's struct) set and every selected pointer of ptrs (t, object, normal) set; occlusion: occluded set.  With
+// n == 0 no pointer is looked at.  RT_OK or RT_E_INVALID with its text in *err.
+constexpr uint32_t kHitAll = 7u;
+constexpr uint32_t kQueryFlags = RT_TIME_KERNELS;
+struct QueryArgs {
+    bool occlusion = false, device = false;
+    const void* rays = nullptr;
+    uint32_t n = 0, channels = 0, flags = 0;
+    bool has_bufs = false;                       // nearest: the rt_hit_buffers struct is not NULL
+    const void* ptrs[3] = {nullptr, nullptr, nullptr};
+    const void* occluded = nullptr;
+};
+int plan_query_args(const QueryArgs& a, const char** err);
+// Workgroups of the launch, by plan_aov_workgroups' rule: one 1024-thread workgroup per 1024 rays, at most two per
+// CU (all resident); the workgroups stride over the rays beyond that.
+uint32_t plan_query_workgroups(uint64_t n, int n_cu);
+
 // ---- streams ----------------------------------------------------------------------------
 struct StreamShape {
     bool split = false;     // shadow + shading kernels on b streams of their own

@@ -2,7 +2,7 @@
 // translation units that implement it share: rt_device.cpp (create / destroy, tuning, probes),
 // rt_scene_upload.cpp, rt_render.cpp (the render path, lanes, reserve, statistics), rt_accum.cpp
 // (progressive rendering: the accumulator and its calls), rt_aov.cpp (first-hit feature buffers: the entry
-// points' checks and the host variant) and rt_copy.cpp (device -> host copies).
+// points' checks and the host variant), rt_query.cpp (ray queries: the same) and rt_copy.cpp (device -> host copies).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -254,6 +254,20 @@ int render_accumulate(rt_ctx* c, const rt_render_opts* o, double* sums, uint32_t
 // rt_render_aov behind its argument checks: one render of o's tile into the selected device buffers of `out`
 // (channels: the rt_aov mask, for the verbose line) on `stream` (null: the context's own).
 int render_aov(rt_ctx* c, const rt_render_opts* o, const AovOut& out, uint32_t channels, void* stream);
+
+// rt_query_nearest / rt_query_occluded behind their argument checks: one render of n rays (device memory, 16-byte
+// aligned) into the selected device buffers on `stream` (null: the context's own).  n == 0: a render that launches
+// nothing.
+struct QueryCall {
+    bool occlusion = false;
+    const double* rays = nullptr;
+    const double* r2 = nullptr;        // occlusion: the squared ranges, or null (no range)
+    bool ranged = false;               // occlusion: the caller gave ranges (r2 itself stays null for an empty batch)
+    uint32_t n = 0, channels = 0, flags = 0;
+    QueryOut out{};                    // nearest: the selected channels (the others null)
+    uint8_t* occluded = nullptr;
+};
+int render_query(rt_ctx* c, const QueryCall& q, void* stream);
 
 // ---- rt_accum.cpp -------------------------------------------------------------------------
 // rt_ctx_destroy: free the device memory of the accumulators still alive and detach them.

@@ -786,6 +786,48 @@ int render_aov(rt_ctx* c, const rt_render_opts* o, const AovOut& out, uint32_t c
     return end_render(c, st, true);
 }
 
+// rt_query_nearest / rt_query_occluded behind their argument checks (rt_query.cpp): a render of the context like
+// every other (the stream's wait for the previous render, as begin_render makes it: a query has no tile geometry
+// for that function to check; end_render), one launch of query_nearest or query_occluded from the source the
+// planner names.  No tile, no pixels, no working set: rays = traced_rays = n.
+int render_query(rt_ctx* c, const QueryCall& q, void* stream) {
+    HIP_TRY(c, hipSetDevice(c->device));
+    const hipStream_t st = stream ? static_cast<hipStream_t>(stream) : c->stream;
+    if (c->render_pending && st != c->done_stream) HIP_TRY(c, hipStreamWaitEvent(st, c->render_done, 0));
+    const SceneFacts sf = scene_facts(c);
+    const QuerySource qs = q.occlusion ? plan_query_occ_source(sf, c->tune) : plan_query_source(sf, c->tune);
+    c->dsc.pfx2 = qs.pfx2;
+    c->tally.on = false;
+    c->last_pixels = 0;
+    c->last_stream = st;
+    c->last_spp_traced = 1;
+    c->last_chunks = 0;
+    c->n_bands = 0;
+    c->sparse_on = false;
+    if (const int rc = zero_counters(c, st); rc != RT_OK) return rc;
+    const uint32_t wgs = plan_query_workgroups(q.n, c->n_cu);
+    if (c->t(kTuneVerbose)) {
+        if (q.occlusion)
+            std::fprintf(stderr, "rtamd: query occluded src %d rays %u range %d workgroups %u\n", qs.src, q.n, q.ranged ? 1 : 0,
+                         q.n ? wgs : 0u);
+        else
+            std::fprintf(stderr, "rtamd: query nearest src %d rays %u channels 0x%x workgroups %u\n", qs.src, q.n, q.channels,
+                         q.n ? wgs : 0u);
+    }
+    c->ev0_set = true;
+    HIP_TRY(c, hipEventRecord(c->ev0, st));
+    if (q.n) {
+        const bool timed = (q.flags & RT_TIME_KERNELS) != 0;
+        LaunchMarks m;
+        m.pool = &c->tev; m.used = &c->t_used; m.out = &c->tint;
+        if (timed) HIP_TRY(c, m.begin(st));
+        if (q.occlusion) HIP_TRY(c, launch_query_occluded(c->dsc, c->d_counters, q.rays, q.r2, q.n, q.occluded, qs.src, wgs, st));
+        else HIP_TRY(c, launch_query_nearest(c->dsc, c->d_counters, q.rays, q.n, q.out, qs.src, wgs, st));
+        if (timed) HIP_TRY(c, m.mark(st, q.occlusion ? kKfOcclusion : kKfNearest));
+    }
+    return end_render(c, st, true);
+}
+
 void drop_lanes(rt_ctx* c) {
     for (auto& L : c->lanes) {
         release_lane_memory(c, L);

@@ -41,6 +41,10 @@ RT_AOV_ALL = 31
 AOV_CHANNELS = {RT_AOV_DEPTH: ("depth", 1, np.float32), RT_AOV_NORMAL: ("normal", 3, np.float32),
                 RT_AOV_ALBEDO: ("albedo", 3, np.float32), RT_AOV_COVERAGE: ("coverage", 1, np.float32),
                 RT_AOV_OBJECT: ("object", 1, np.int32)}
+RT_HIT_T, RT_HIT_OBJECT, RT_HIT_NORMAL = 1, 2, 4      # rt_hit_channel
+RT_HIT_ALL = 7
+# rt_hit_channel bit -> (rt_hit_buffers field, elements per ray, dtype)
+HIT_CHANNELS = {RT_HIT_T: ("t", 1, np.float64), RT_HIT_OBJECT: ("object", 1, np.int32), RT_HIT_NORMAL: ("normal", 3, np.float64)}
 RT_MAX_DEPTH_LIMIT = 30
 
 
@@ -100,6 +104,10 @@ class rt_aov_buffers(C.Structure):
                 ("object", C.c_void_p)]
 
 
+class rt_hit_buffers(C.Structure):
+    _fields_ = [("t", C.c_void_p), ("object", C.c_void_p), ("normal", C.c_void_p)]
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise ImportError(f"{LIB_PATH} is missing: run `make -C rust-raytrace_amd` "
@@ -132,6 +140,14 @@ def _load():
         "rt_ctx_stats": (C.c_int, [C.c_void_p, P(rt_stats)]),
         "rt_render_aov": (C.c_int, [C.c_void_p, P(rt_render_opts), C.c_uint32, P(rt_aov_buffers), P(rt_stats)]),
         "rt_render_aov_device": (C.c_int, [C.c_void_p, P(rt_render_opts), C.c_uint32, P(rt_aov_buffers), C.c_void_p]),
+        "rt_query_nearest": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, P(rt_hit_buffers), C.c_uint32,
+                                       P(rt_stats)]),
+        "rt_query_occluded": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32,
+                                        P(rt_stats)]),
+        "rt_query_nearest_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, P(rt_hit_buffers),
+                                              C.c_uint32, C.c_void_p]),
+        "rt_query_occluded_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32,
+                                               C.c_void_p]),
         "rt_accum_create": (C.c_int, [C.c_void_p, P(rt_render_opts), P(C.c_void_p)]),
         "rt_accum_destroy": (None, [C.c_void_p]),
         "rt_accum_samples": (C.c_int, [C.c_void_p, P(C.c_uint32)]),
@@ -507,6 +523,66 @@ class Context:
                 raise TypeError(f"unknown AOV channel {name}")
             setattr(bufs, name, ptr or None)
         _check(lib.rt_render_aov_device(self._h, C.byref(opts), int(channels), C.byref(bufs), C.c_void_p(stream_ptr or 0)),
+               self._h)
+
+    def query_nearest(self, rays, channels=RT_HIT_ALL, out=None, stats=True, flags=0):
+        """rt_query_nearest: Scene::intersect for caller-supplied rays (synchronous) -> ({name: array}, stats).
+        rays: anything np.ascontiguousarray(.., float64) turns into [n, 6] (origin, direction; not normalised).
+        Arrays: t float64 [n] (+inf: miss), object int32 [n] (-1: miss), normal float64 [n, 3] (the shape's, not
+        oriented); only the selected channels.  out: {name: array} to write into instead (a selected channel
+        missing from it is passed as NULL: the call is refused)."""
+        r = np.ascontiguousarray(rays, dtype=np.float64).reshape(-1, 6)
+        n = r.shape[0]
+        arrays, bufs = {}, rt_hit_buffers()
+        for bit, (name, k, dt) in HIT_CHANNELS.items():
+            if out is not None:
+                a = out.get(name)
+                if a is not None:
+                    assert a.dtype == dt and a.size >= n * k and a.flags.c_contiguous
+            elif channels & bit:
+                a = np.zeros((n, k) if k > 1 else (n,), dt)
+            else:
+                a = None
+            if a is not None:
+                arrays[name] = a
+                setattr(bufs, name, a.ctypes.data)
+        st = rt_stats() if stats else None
+        _check(lib.rt_query_nearest(self._h, r.ctypes.data, n, int(channels), C.byref(bufs), int(flags),
+                                    C.byref(st) if stats else None), self._h)
+        return arrays, st
+
+    def query_occluded(self, rays, r2=None, out=None, stats=True, flags=0):
+        """rt_query_occluded: the shadow test of raytrace.rs:43-50 for caller-supplied rays (synchronous) ->
+        (uint8 [n], stats).  r2: None (any hit occludes: the directional light's rule) or the squared ranges [n]
+        (occluded when t * t < r2: the point light's).  out: a uint8 array to write into instead."""
+        r = np.ascontiguousarray(rays, dtype=np.float64).reshape(-1, 6)
+        n = r.shape[0]
+        rr = None
+        if r2 is not None:
+            rr = np.ascontiguousarray(r2, dtype=np.float64).reshape(-1)
+            assert rr.shape == (n,)
+        occ = np.zeros(n, np.uint8) if out is None else out
+        assert occ.dtype == np.uint8 and occ.size >= n and occ.flags.c_contiguous
+        st = rt_stats() if stats else None
+        _check(lib.rt_query_occluded(self._h, r.ctypes.data, rr.ctypes.data if rr is not None else None, n,
+                                     occ.ctypes.data, int(flags), C.byref(st) if stats else None), self._h)
+        return occ, st
+
+    def query_nearest_device(self, d_rays_ptr, n, channels, ptrs, stream_ptr=None, flags=0):
+        """rt_query_nearest_device: asynchronous; d_rays_ptr: raw device pointer of [n, 6] float64 rays (16-byte
+        aligned), ptrs: {name: raw device pointer} for the channels' names t, object, normal."""
+        bufs = rt_hit_buffers()
+        for name, ptr in ptrs.items():
+            if name not in [v[0] for v in HIT_CHANNELS.values()]:
+                raise TypeError(f"unknown hit channel {name}")
+            setattr(bufs, name, ptr or None)
+        _check(lib.rt_query_nearest_device(self._h, C.c_void_p(d_rays_ptr or 0), int(n), int(channels), C.byref(bufs),
+                                           int(flags), C.c_void_p(stream_ptr or 0)), self._h)
+
+    def query_occluded_device(self, d_rays_ptr, d_r2_ptr, n, d_occluded_ptr, stream_ptr=None, flags=0):
+        """rt_query_occluded_device: asynchronous; raw device pointers (d_r2_ptr None / 0: no range)."""
+        _check(lib.rt_query_occluded_device(self._h, C.c_void_p(d_rays_ptr or 0), C.c_void_p(d_r2_ptr or 0), int(n),
+                                            C.c_void_p(d_occluded_ptr or 0), int(flags), C.c_void_p(stream_ptr or 0)),
                self._h)
 
     def reserve(self, opts, host=False, stream_ptr=None):
