@@ -258,19 +258,82 @@ __host__ __device__ inline int32_t prefix_nodes(const DevScene& sc) {
     return 0;
 }
 
+// The scene constants a grid source stages behind its spheres (stage_grid_consts): one LdsGridHdr
+// per light and the DevLight array (shadow grids), or the camera grid's one header; then the planes
+// and their object ids when there are at most kStagedPlanes.  The shadow mask has 32 bits, so at
+// most 32 * (240 + 104) B = 10.75 KB of headers and lights and 416 B of planes: with the planner's
+// 64 KB (shadow) and 72 KB (camera) sphere limits and the queue words a workgroup stays below
+// half a CU's 160 KB up to ~20 lights at G = 512, and far below the launch limit always.
+template <int kSrc>
+__host__ __device__ inline size_t grid_const_bytes(const DevScene& sc) {
+    if (!Src<kSrc>::grid && !Src<kSrc>::cgrid) return 0;
+    const size_t nh = Src<kSrc>::grid ? static_cast<size_t>(sc.n_lights) : 1;
+    size_t bytes = nh * sizeof(LdsGridHdr) + (Src<kSrc>::grid ? nh * sizeof(DevLight) : 0);
+    if (sc.n_planes <= kStagedPlanes) bytes += static_cast<size_t>(sc.n_planes) * (sizeof(DevPlane) + sizeof(int32_t));
+    return bytes;
+}
+
 // LDS layout of the intersection kernels: [staged data][region scan, G + 1][wave sums, 16][counter].
 template <int kSrc>
 __host__ __device__ inline size_t staged_bytes(const DevScene& sc) {
+    if (Src<kSrc>::grid || Src<kSrc>::cgrid) {
+        const size_t per = kSrc == kSrcGridL ? sizeof(DevSphere) : kSrc == kSrcCamGridL ? sizeof(DevSphere) + sizeof(int32_t) : 0;
+        const size_t sph = (static_cast<size_t>(sc.n_spheres) * per + 15) / 16 * 16;
+        return (sph + grid_const_bytes<kSrc>(sc) + 15) / 16 * 16;
+    }
     size_t bytes = 0;
     if (Src<kSrc>::q4) bytes = static_cast<size_t>(prefix_nodes<kSrc>(sc)) * sizeof(DevQNode4);
-    if (kSrc == kSrcLds || kSrc == kSrcGridL) bytes = static_cast<size_t>(sc.n_spheres) * sizeof(DevSphere);
-    if (kSrc == kSrcCamGridL) bytes = static_cast<size_t>(sc.n_spheres) * (sizeof(DevSphere) + sizeof(int32_t));
+    if (kSrc == kSrcLds) bytes = static_cast<size_t>(sc.n_spheres) * sizeof(DevSphere);
     if (kSrc == kSrcBvhP) bytes = static_cast<size_t>(prefix_nodes<kSrc>(sc)) * sizeof(DevBvhNode);
     if (Src<kSrc>::half) bytes = static_cast<size_t>(prefix_nodes<kSrc>(sc)) * sizeof(DevBvhNodeH);
     if (Src<kSrc>::nodes == 2)
         bytes = Src<kSrc>::wide ? static_cast<size_t>(sc.n_bvh4) * kBvh4Planes * sizeof(DevBvh4Plane) : node_planes_bytes(sc.n_bvh);
     if (Src<kSrc>::bvh && Src<kSrc>::sph_lds) bytes += static_cast<size_t>(sc.n_spheres) * (sizeof(DevSphere) + sizeof(int32_t));
     return (bytes + 15) / 16 * 16;
+}
+
+// Stage a grid source's scene constants at `at` (16-byte aligned; grid_const_bytes): headers,
+// lights, planes, plane ids, in that order.  Eight work-items per header: one per face (the
+// face's five words gathered from DevLightGrid's per-field arrays) and one for the rest.
+template <int kSrc>
+__device__ __forceinline__ void stage_grid_consts(const DevScene& sc, unsigned char* at, BvhView& v) {
+    constexpr int T = kWfThreads;
+    const DevLightGrid* src = Src<kSrc>::grid ? sc.lgrid : sc.cgrid;
+    const int nh = Src<kSrc>::grid ? sc.n_lights : 1;
+    LdsGridHdr* hdr = reinterpret_cast<LdsGridHdr*>(at);
+    if (src)
+        for (int i = threadIdx.x; i < nh * 8; i += T) {
+            const DevLightGrid& g = src[i >> 3];
+            LdsGridHdr& h = hdr[i >> 3];
+            const int f = i & 7;
+            if (f < 6) {
+                h.face[f] = LdsGridFace{g.fx0[f], g.fy0[f], g.fw[f], g.fh[f], g.off_base[f], {0u, 0u, 0u}};
+            } else if (f == 6) {
+                h.lx = g.lx; h.ly = g.ly; h.lz = g.lz;
+                h.R = g.R; h.always_begin = g.always_begin; h.always_end = g.always_end;
+            }
+        }
+    v.ghdr = hdr;
+    at += static_cast<size_t>(nh) * sizeof(LdsGridHdr);
+    if constexpr (Src<kSrc>::grid) {
+        static_assert(sizeof(DevLight) % 8 == 0, "DevLight is copied as 8-byte words");
+        uint64_t* ll = reinterpret_cast<uint64_t*>(at);
+        const uint64_t* gl = reinterpret_cast<const uint64_t*>(sc.lights);
+        const int nw = nh * static_cast<int>(sizeof(DevLight) / 8);
+        for (int i = threadIdx.x; i < nw; i += T) ll[i] = gl[i];
+        v.llights = reinterpret_cast<const DevLight*>(at);
+        at += static_cast<size_t>(nh) * sizeof(DevLight);
+    }
+    if (sc.n_planes > 0 && sc.n_planes <= kStagedPlanes) {
+        uint64_t* lp = reinterpret_cast<uint64_t*>(at);
+        const uint64_t* gp = reinterpret_cast<const uint64_t*>(sc.planes);
+        const int nw = sc.n_planes * static_cast<int>(sizeof(DevPlane) / 8);
+        for (int i = threadIdx.x; i < nw; i += T) lp[i] = gp[i];
+        int32_t* lo = reinterpret_cast<int32_t*>(lp + nw);
+        for (int i = threadIdx.x; i < sc.n_planes; i += T) lo[i] = sc.plane_obj[i];
+        v.lplanes = reinterpret_cast<const DevPlane*>(lp);
+        v.lplane_obj = lo;
+    }
 }
 
 // Stage what the source keeps in LDS (the whole tree and the spheres, or the
@@ -308,6 +371,8 @@ __device__ __forceinline__ BvhView stage_lds(const DevScene& sc, unsigned char* 
         DevSphere* ls = reinterpret_cast<DevSphere*>(lds);
         for (int i = threadIdx.x; i < sc.n_spheres; i += T) ls[i] = sc.spheres[i];
         v.sph = ls;
+        if constexpr (kSrc == kSrcGridL)
+            stage_grid_consts<kSrc>(sc, lds + (static_cast<size_t>(sc.n_spheres) * sizeof(DevSphere) + 15) / 16 * 16, v);
         return v;
     } else if constexpr (kSrc == kSrcCamGridL) {
         DevSphere* ls = reinterpret_cast<DevSphere*>(lds);
@@ -315,6 +380,10 @@ __device__ __forceinline__ BvhView stage_lds(const DevScene& sc, unsigned char* 
         for (int i = threadIdx.x; i < sc.n_spheres; i += T) { ls[i] = sc.spheres[i]; lo[i] = sc.sphere_obj[i]; }
         v.sph = ls;
         v.obj = lo;
+        stage_grid_consts<kSrc>(sc, lds + (static_cast<size_t>(sc.n_spheres) * (sizeof(DevSphere) + sizeof(int32_t)) + 15) / 16 * 16, v);
+        return v;
+    } else if constexpr (kSrc == kSrcGridG || kSrc == kSrcCamGridG) {
+        stage_grid_consts<kSrc>(sc, lds, v);
         return v;
     } else if constexpr (Src<kSrc>::nodes == 2 && Src<kSrc>::wide) {
         DevBvh4Plane* lp = reinterpret_cast<DevBvh4Plane*>(lds);
@@ -351,7 +420,7 @@ __device__ __forceinline__ BvhView stage_lds(const DevScene& sc, unsigned char* 
 // Scene::intersect of one ray through the source's structure (scene.rs:247-249).
 template <int kSrc, bool kCount>
 __device__ __forceinline__ Hit nearest_any(const DevScene& sc, const BvhView& v, const Ray& r, Work* w) {
-    if constexpr (Src<kSrc>::cgrid) return nearest_cgrid<kCount>(sc, v, r, w);
+    if constexpr (Src<kSrc>::cgrid) return nearest_cgrid<kCount>(sc, v, r, w);       // stage_lds staged the header
     else if constexpr (Src<kSrc>::q4) return nearest_q4<kCount, kSrc == kSrcQ4>(sc, v, r, w);
     // two stack entries in registers when the tree is read through L2 below its LDS prefix
     // (C4 74.0 -> 71.4 ms); RT_COMPACT_REG on the compact stack with the whole tree in LDS (the

@@ -28,50 +28,78 @@ __global__ __launch_bounds__(kWfThreads, Src<kSrc>::waves) void wf_occlusion(Dev
     const size_t rk = static_cast<size_t>(k) * b.qcap;
     // light-major: a wave traces 64 consecutive records toward ONE light (coherent).
     // Software pipelined: the next chunk's shade points are loaded (HBM) before this
-    // chunk's queries run, so their latency hides behind the list walks.
+    // chunk's queries run.  The grid sources take everything else a query needs before its
+    // list walk from LDS, so the chunk's first wait on vector memory comes after the
+    // own-sphere test and these loads have that long to arrive.
     const uint32_t W = b.G * (kWfThreads / 64), lane = threadIdx.x & 63u;
+    // qi / nrec by a multiply with floor(2^32 / nrec) kept in a scalar register (the estimate
+    // is at most 2 low: two corrections); entries stay 32-bit (entry < qcap <= capa, a u32)
+    const uint32_t nrec_s = __builtin_amdgcn_readfirstlane(nrec);
+    const uint32_t magic = __builtin_amdgcn_readfirstlane(
+        nrec_s > 1u ? static_cast<uint32_t>((1ull << 32) / nrec_s) : 0xFFFFFFFFu);
     auto item_at = [&](uint32_t qi, uint32_t& l) {
-        l = qi / nrec;
-        return rk + region_entry(ql.scan, b.G, b.R, qi - l * nrec);
+        uint32_t q = __umulhi(qi, magic), rem = qi - q * nrec_s;
+        if (rem >= nrec_s) { ++q; rem -= nrec_s; }
+        if (rem >= nrec_s) { ++q; rem -= nrec_s; }
+        l = q;
+        return static_cast<uint32_t>(region_entry(ql.scan, b.G, b.R, rem));
     };
+    // Source 15 (spheres through L2, in registers) has no room for the prefetched words at its 64
+    // VGPRs: they were spilled, with a wait behind their loads.  It loads a chunk's points when
+    // it starts the chunk.
+    constexpr bool kAhead = kSrc != kSrcGridG;
     uint32_t rc = wave_slot(b, n), lc = 0;
-    size_t atc = 0;
+    uint32_t atc = 0;
     double pc[3] = {0.0, 0.0, 0.0};
     int32_t hc = -1;
-    if (static_cast<uint64_t>(rc) * 64u + lane < n) {
+    if (kAhead && static_cast<uint64_t>(rc) * 64u + lane < n) {
         atc = item_at(rc * 64u + lane, lc);
-        pc[0] = ldn_if<3>(&b.rf(0)[atc]); pc[1] = ldn_if<3>(&b.rf(1)[atc]); pc[2] = ldn_if<3>(&b.rf(2)[atc]);
-        hc = static_cast<int32_t>(b.ru(1)[atc]);
+        const size_t at = rk + atc;
+        pc[0] = ldn_if<3>(&b.rf(0)[at]); pc[1] = ldn_if<3>(&b.rf(1)[at]); pc[2] = ldn_if<3>(&b.rf(2)[at]);
+        hc = static_cast<int32_t>(b.ru(1)[at]);
     }
+    // The first chunk needs these at once anyway.  Waiting for them here, before the loop, keeps
+    // the loop's own waits exact: with loads pending on entry the compiler waits for the loop's
+    // prefetch right behind its issue, on every chunk.
+    asm volatile("" :: "v"(pc[0]), "v"(pc[1]), "v"(pc[2]), "v"(hc));
     for (; static_cast<uint64_t>(rc) * 64u < n; rc += W) {
-        const uint64_t qn = static_cast<uint64_t>(rc + W) * 64u + lane;
+        const uint64_t qn = static_cast<uint64_t>(kAhead ? rc + W : rc) * 64u + lane;
         uint32_t ln = 0;
-        size_t atn = 0;
+        uint32_t atn = 0;
         double pn[3] = {0.0, 0.0, 0.0};
         int32_t hn = -1;
         if (qn < n) {
             atn = item_at(static_cast<uint32_t>(qn), ln);
-            pn[0] = ldn_if<3>(&b.rf(0)[atn]); pn[1] = ldn_if<3>(&b.rf(1)[atn]); pn[2] = ldn_if<3>(&b.rf(2)[atn]);
-            hn = static_cast<int32_t>(b.ru(1)[atn]);
+            const size_t at = rk + atn;
+            pn[0] = ldn_if<3>(&b.rf(0)[at]); pn[1] = ldn_if<3>(&b.rf(1)[at]); pn[2] = ldn_if<3>(&b.rf(2)[at]);
+            hn = static_cast<int32_t>(b.ru(1)[at]);
         }
+        if constexpr (!kAhead) { lc = ln; atc = atn; pc[0] = pn[0]; pc[1] = pn[1]; pc[2] = pn[2]; hc = hn; }
         const uint32_t qi = rc * 64u + lane;
         const uint32_t l = lc;
-        const size_t at = atc;
+        const size_t at = rk + atc;
         const double ptx = pc[0], pty = pc[1], ptz = pc[2];
         const int32_t hint = hc;
-        lc = ln; atc = atn; pc[0] = pn[0]; pc[1] = pn[1]; pc[2] = pn[2]; hc = hn;
+        if constexpr (kAhead) { lc = ln; atc = atn; pc[0] = pn[0]; pc[1] = pn[1]; pc[2] = pn[2]; hc = hn; }
         if (qi >= n) continue;
         double lx, ly, lz, r2;
-        const bool has_range = light_dir(sc.lights[l], ptx, pty, ptz, lx, ly, lz, r2);
-        const Ray sray{ptx + lx * kEps, pty + ly * kEps, ptz + lz * kEps, lx, ly, lz};
         // the sphere the point lies on is tested first (it shadows every light behind its surface)
         bool occluded;
-        if constexpr (Src<kSrc>::grid)          // the host checked: every light has a grid
-            occluded = occluded_lgrid<kCount>(sc, v, sc.lgrid[l], sray, r2, ptx, pty, ptz, hint, &w);
-        else
+        if constexpr (Src<kSrc>::grid) {        // the host checked: every light has a grid
+            // light and grid header from LDS (stage_lds); the cell's offsets are requested first
+            // and travel during the light direction, the planes and the own-sphere test
+            const LdsGridHdr& g = v.ghdr[l];
+            const GridReq q = lgrid_request(sc, g, ptx, pty, ptz);
+            (void)light_dir(v.llights[l], ptx, pty, ptz, lx, ly, lz, r2);
+            const Ray sray{ptx + lx * kEps, pty + ly * kEps, ptz + lz * kEps, lx, ly, lz};
+            occluded = occluded_lgrid_lds<kCount>(sc, v, g, q, sray, r2, hint, &w);
+        } else {
+            const bool has_range = light_dir(sc.lights[l], ptx, pty, ptz, lx, ly, lz, r2);
+            const Ray sray{ptx + lx * kEps, pty + ly * kEps, ptz + lz * kEps, lx, ly, lz};
             occluded = has_range && sc.lgrid && sc.lgrid[l].R > 0
                            ? occluded_lgrid<kCount>(sc, v, sc.lgrid[l], sray, r2, ptx, pty, ptz, hint, &w)
                            : occluded_any<kSrc, kCount>(sc, v, sray, has_range, r2, hint, &w);
+        }
         if (occluded) atomicOr(&b.ru(3)[at], 1u << l);
     }
     flush_work<kCount>(b, 4, w);
