@@ -69,6 +69,8 @@ extern "C" {
  * Still 10: the ray queries (enum rt_hit_channel, rt_hit_buffers, rt_query_nearest / rt_query_occluded and their
  * device variants) add functions, one enum and one struct, and alter nothing a caller built against ABI 10 passes
  * or reads; RT_KF_COUNT is still 8.  A caller that needs them looks the symbols up.
+ * Still 10: the denoiser (enum rt_denoise_flags, rt_denoise_params, rt_denoise_inputs, rt_denoise and
+ * rt_denoise_device) adds functions, one enum and two structs in the same way; no tuning key.
  * 9: first-hit feature buffers: enum rt_aov, rt_aov_buffers, rt_render_aov and rt_render_aov_device
  * (depth, normal, albedo, coverage and object id of the camera rays' first hits).  Functions and types
  * added only: no struct, enum value or tuning key changed, RT_KF_COUNT is still 8.
@@ -454,6 +456,72 @@ int rt_query_nearest_device(rt_ctx* ctx, const double* d_rays, uint32_t n, uint3
                             uint32_t flags, void* stream);
 int rt_query_occluded_device(rt_ctx* ctx, const double* d_rays, const double* d_r2, uint32_t n, uint8_t* d_occluded,
                              uint32_t flags, void* stream);
+/* ---- denoiser: an edge-avoiding a-trous wavelet filter guided by the first-hit feature buffers ----
+ * What a caller does with a 4- or 16-sample frame of a noisy scene (IndirectPhong, AreaLight, random jitter) and
+ * the buffers rt_render_aov gives for it: `iterations` passes of the 5x5 B3-spline kernel with holes (Dammertz et
+ * al. 2010), pass i with step s = 2^i, every tap's weight cut down where normal, depth or colour differ.  Not a
+ * render: no scene is needed, and rt_ctx_stats / rt_ctx_generation_counts are left as they were.
+ *
+ * The rule.  All arithmetic is IEEE f64 + - * / and comparisons, never fused, in exactly this order; every f32
+ * read is widened to f64 first.
+ * Inputs, each tight row-major as rt_render_device / rt_render_aov_device write a whole-frame tile: rgb [h, w, 3]
+ *   f32; the guides, each read only when its flag is set: normal [h, w, 3], depth [h, w], albedo [h, w, 3] f32.
+ * Demodulation (RT_DN_DEMODULATE), per channel before the first pass: c = a > 0.0 ? (double)(float)(c / a) : c.
+ * Pass i at pixel p: sum = (0, 0, 0), wsum = 0; for dy = -2 .. 2 (outer), dx = -2 .. 2 (inner) the tap is
+ *   q = p + s * (dx, dy); a tap outside the image is skipped.
+ *     kw = K[|dy|] * K[|dx|], K = {3/8, 1/4, 1/16}
+ *     the centre tap (q == p): wt = kw; it is never skipped.
+ *     any other tap: wt = kw, then for the flags that are set, in this order,
+ *       RT_DN_NORMAL  d = (nx_p*nx_q + ny_p*ny_q) + nz_p*nz_q;  d = d > 0.0 ? d : 0.0;  normal_squarings times
+ *                     d = d*d;  wt = wt*d
+ *       RT_DN_DEPTH   dz = z_p - z_q;  t = sigma_depth * (double)s;  wt = wt / (1.0 + (dz*dz)/(t*t))
+ *       RT_DN_COLOR   dr, dg, db = c_p - c_q per channel (this pass's input colours);  e = (dr*dr + dg*dg) + db*db;
+ *                     sc = sigma_color / (double)s;  wt = wt / (1.0 + e/(sc*sc))
+ *       and the tap is skipped unless wt > 0.0 and all three channels of c_q are finite.
+ *     a kept tap: sum_ch = sum_ch + wt*c_q_ch;  wsum = wsum + wt.
+ *   v_ch = sum_ch / wsum.  Between passes v is rounded once to f32.
+ * After the last pass, in f64 (RT_DN_DEMODULATE): v = a > 0.0 ? v*a : v.  out_rgb = (float)v; out_bgr = the sRGB
+ *   byte of the f64 value v, B G R, as every pixel writer of the library forms it; rows of bgr_pitch bytes
+ *   (0 -> 3*width) whose bytes past the pixels are left alone, as rt_render_device leaves them.
+ * What follows from it: a non-finite pixel keeps to itself (its neighbours skip it, and it is its own centre
+ *   tap); a pixel whose guide is NaN (a plane's 0/0 depth) keeps its own colour and is skipped by its neighbours
+ *   (every weight but the centre's is NaN); miss pixels (normal 0) average only with themselves unless
+ *   RT_DN_NORMAL is off.  A -0.0 that is kept comes back as +0.0 (the sums start from +0.0).  flags 0 is a plain
+ *   B3 blur.
+ *
+ * variant: 0 the library's choice, 1 every pass reads its taps through L2 (direct), 2 the passes of steps 1 and 2
+ *   stage the workgroup's tile and halo in LDS (later passes are direct in both).  The results are the same bits.
+ * Scratch (two colour images and one guide image, 16 B per pixel each) belongs to the context, grows on demand
+ *   and is freed by rt_ctx_destroy; RT_E_NOMEM when it does not fit.  Because it is shared, a call is ordered on
+ *   the device after the context's previous denoise, whatever stream that ran on.
+ * RT_E_INVALID, before anything changes: a null argument; width or height 0; iterations outside 1..8; unknown flag
+ *   bits; normal_squarings > 10; variant > 2; a selected guide's pointer NULL (albedo for RT_DN_DEMODULATE); a
+ *   selected sigma (sigma_depth with RT_DN_DEPTH, sigma_color with RT_DN_COLOR) that is not finite and > 0; both
+ *   outputs NULL; a nonzero bgr_pitch below 3*width; out_rgb == rgb. */
+enum rt_denoise_flags { RT_DN_NORMAL = 1, RT_DN_DEPTH = 2, RT_DN_COLOR = 4, RT_DN_DEMODULATE = 8 };
+typedef struct {
+    uint32_t width, height;
+    uint32_t iterations;        /* 1..8: pass i has step 2^i */
+    uint32_t flags;             /* rt_denoise_flags */
+    uint32_t normal_squarings;  /* 0..10: the normal weight is max(dot, 0)^(2^normal_squarings) */
+    uint32_t variant;           /* 0 auto, 1 direct, 2 LDS tiles at steps 1 and 2 */
+    uint32_t bgr_pitch;         /* bytes per output BGR row; 0 -> 3*width */
+    uint32_t _pad;
+    double sigma_color;
+    double sigma_depth;
+} rt_denoise_params;
+typedef struct {
+    const float* rgb;
+    const float* normal;
+    const float* depth;
+    const float* albedo;
+} rt_denoise_inputs;
+/* Asynchronous on `stream` (NULL: the context's own), DEVICE buffers; either output may be NULL, not both. */
+int rt_denoise_device(rt_ctx* ctx, const rt_denoise_params* params, const rt_denoise_inputs* dev, float* d_out_rgb,
+                      uint8_t* d_out_bgr, void* stream);
+/* Synchronous, HOST buffers: device buffers allocated, filled, filtered, copied back and freed.  No performance claim. */
+int rt_denoise(rt_ctx* ctx, const rt_denoise_params* params, const rt_denoise_inputs* host, float* out_rgb,
+               uint8_t* out_bgr);
 /* ---- progressive rendering (main.rs:47-56 split over calls) ----
  * The reference's pixel is `res = BLACK; for _ in 0..antialias { res = res + raytrace(..) }; res / antialias`
  * (main.rs:47-56).  An rt_accum keeps `res` of every pixel of one tile on the device between calls: f64

@@ -170,6 +170,30 @@ hipError_t launch_query_nearest(const DevScene& sc, unsigned long long* counters
 hipError_t launch_query_occluded(const DevScene& sc, unsigned long long* counters, const double* rays, const double* r2,
                                  uint32_t n, uint8_t* occluded, int src, uint32_t workgroups, hipStream_t s);
 
+// The denoiser (wf_denoise.hip, rt_denoise_device; the rule: include/raytrace_amd.h).  Device images of w x h
+// pixels.  DnRec: one 16-byte record per pixel, a colour (r, g, b, unused) or a guide (normal x, y, z, depth).
+struct alignas(16) DnRec {
+    float x, y, z, w;
+};
+struct DnFilter {
+    uint32_t w, h;
+    uint32_t flags, squarings;      // rt_denoise_flags, rt_denoise_params::normal_squarings
+    double sigma_color, sigma_depth;
+};
+// The pack pass: the caller's tight f32 images (normal / depth null where their flag is off: zeros; albedo read under
+// RT_DN_DEMODULATE only) into one colour and one guide record per pixel.
+hipError_t launch_denoise_pack(const DnFilter& f, const float* rgb, const float* normal, const float* depth,
+                               const float* albedo, DnRec* colour, DnRec* guide, hipStream_t s);
+// One filter pass of step `step` from `src` into `dst`; lds: the tile-staging form (step <= kDnLdsMaxStep only,
+// else hipErrorInvalidValue).  grid: the plan's (one workgroup per kDnTileW x kDnTileH tile).
+hipError_t launch_denoise_pass(const DnFilter& f, uint32_t step, bool lds, const DnRec* src, const DnRec* guide, DnRec* dst,
+                               uint32_t grid_x, uint32_t grid_y, hipStream_t s);
+// The last pass: as above, then remodulated by `albedo` (RT_DN_DEMODULATE) and written as f32 (out_rgb, tight; may be
+// null) and sRGB B G R bytes (out_bgr, rows of bgr_pitch bytes, padding left alone; may be null).
+hipError_t launch_denoise_last(const DnFilter& f, uint32_t step, bool lds, const DnRec* src, const DnRec* guide,
+                               const float* albedo, float* out_rgb, uint8_t* out_bgr, uint32_t bgr_pitch, uint32_t grid_x,
+                               uint32_t grid_y, hipStream_t s);
+
 // The general path (path_kernel.hip): every material / light / camera class,
 // keyed random draws, one work-item per pixel over the HBM recursion stack.
 // staged: binary BVH + spheres in LDS (path_lds_bytes(sc, true) must fit).

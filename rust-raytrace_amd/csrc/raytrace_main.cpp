@@ -11,7 +11,13 @@
 //            [--max-depth D] [--gpus N] [--band ROWS] [--jitter random|center] [--seed N]
 //            [--algo auto|wavefront|wavefront-aa|path|lds|global]
 //            [--progressive K] [--checkpoint FILE] [--aov PREFIX]
+//            [--denoise ITER] [--denoise-flags normal,depth,color,demodulate|none]
 //
+// --denoise ITER: the image goes through the edge-avoiding a-trous filter (rt_denoise, ITER passes 1..8) before it is
+// written: the frame is rendered with its f32 colours, the first-hit feature buffers with the same --spp, --jitter
+// and --seed (rt_render_aov), and the BMP holds the filter's bytes.  --denoise-flags (default normal,depth) names the
+// guides; normal_squarings 5, sigma_depth 0.05, sigma_color 1.0.  With --progressive every written frame is
+// denoised.  Single-device; a DepthOfFieldCamera has no feature buffers and is refused.
 // --aov PREFIX: instead of the image, the first-hit feature buffers of the frame (rt_render_aov; --spp, --jitter,
 // --seed, --width, --height apply) as PFM files (portable float map: "PF" 3 channels / "Pf" 1 channel, width
 // height, scale -1.0 = little-endian, rows bottom-up, which is the library's row order): PREFIX.depth.pfm,
@@ -49,7 +55,26 @@ struct Args {
     long progressive = 0;              // samples per step (0: one render)
     std::string checkpoint;
     std::string aov;                   // --aov PREFIX: write the feature buffers instead of the image
+    long denoise = 0;                  // --denoise ITER: filter passes (0: off)
+    unsigned denoise_flags = RT_DN_NORMAL | RT_DN_DEPTH;
+    bool bad_denoise_flags = false;
 };
+
+// "normal,depth,color,demodulate" (any subset, any order) or "none" -> rt_denoise_flags; false: an unknown word.
+bool parse_denoise_flags(const std::string& text, unsigned& flags) {
+    flags = 0;
+    if (text == "none") return true;
+    std::stringstream ss(text);
+    std::string w;
+    while (std::getline(ss, w, ',')) {
+        if (w == "normal") flags |= RT_DN_NORMAL;
+        else if (w == "depth") flags |= RT_DN_DEPTH;
+        else if (w == "color") flags |= RT_DN_COLOR;
+        else if (w == "demodulate") flags |= RT_DN_DEMODULATE;
+        else return false;
+    }
+    return true;
+}
 
 bool parse_args(int argc, char** argv, Args& a) {
     for (int i = 1; i < argc; ++i) {
@@ -68,6 +93,8 @@ bool parse_args(int argc, char** argv, Args& a) {
         else if (k == "--progressive" && (v = val())) a.progressive = std::atol(v);
         else if (k == "--checkpoint" && (v = val())) a.checkpoint = v;
         else if (k == "--aov" && (v = val())) a.aov = v;
+        else if (k == "--denoise" && (v = val())) a.denoise = std::atol(v);
+        else if (k == "--denoise-flags" && (v = val())) a.bad_denoise_flags = !parse_denoise_flags(v, a.denoise_flags);
         else if (k == "--jitter" && (v = val())) a.jitter = std::string(v) == "center" ? RT_JITTER_CENTER : RT_JITTER_RANDOM;
         else if (k == "--algo" && (v = val())) {
             std::string s = v;
@@ -78,7 +105,8 @@ bool parse_args(int argc, char** argv, Args& a) {
             std::fprintf(stderr, "usage: raytrace [--scene FILE] [--out FILE] [--width W] [--height H] [--spp N]\n"
                                  "                [--max-depth D] [--gpus N] [--band ROWS] [--jitter random|center]\n"
                                  "                [--seed N] [--algo auto|wavefront|wavefront-aa|path|lds|global]\n"
-                                 "                [--progressive K] [--checkpoint FILE] [--aov PREFIX]\n");
+                                 "                [--progressive K] [--checkpoint FILE] [--aov PREFIX]\n"
+                                 "                [--denoise ITER] [--denoise-flags normal,depth,color,demodulate|none]\n");
             return false;
         }
     }
@@ -89,6 +117,62 @@ uint64_t fnv1a64(const std::string& text) {
     uint64_t h = 0xcbf29ce484222325ull;
     for (unsigned char ch : text) h = (h ^ ch) * 0x100000001b3ull;
     return h;
+}
+
+// --denoise: the guides of the frame (rendered once, with the image's spp, jitter and seed) and the filter's settings.
+struct Denoiser {
+    std::vector<float> normal, depth, albedo;
+    rt_denoise_params p{};
+    // the guides from rt_render_aov; false: refused (rt_last_error(ctx) says why, e.g. a DepthOfFieldCamera)
+    bool setup(rt_ctx* ctx, const Args& a, uint32_t W, uint32_t H, uint32_t spp, uint32_t pitch) {
+        const size_t n = static_cast<size_t>(W) * H;
+        normal.resize(3 * n); depth.resize(n); albedo.resize(3 * n);
+        p.width = W; p.height = H; p.iterations = static_cast<uint32_t>(a.denoise); p.flags = a.denoise_flags;
+        p.normal_squarings = 5; p.variant = 0; p.bgr_pitch = pitch;
+        p.sigma_color = 1.0; p.sigma_depth = 0.05;
+        rt_render_opts o;
+        rt_render_opts_default(&o, W, H);
+        o.spp = spp; o.jitter = a.jitter; o.seed = a.seed;
+        const rt_aov_buffers b{depth.data(), normal.data(), albedo.data(), nullptr, nullptr};
+        return rt_render_aov(ctx, &o, RT_AOV_DEPTH | RT_AOV_NORMAL | RT_AOV_ALBEDO, &b, nullptr) == RT_OK;
+    }
+    // rgb (tight f32) -> the BMP rows of `frame`
+    bool run(rt_ctx* ctx, const float* rgb, uint8_t* frame) const {
+        const rt_denoise_inputs in{rgb, normal.data(), depth.data(), albedo.data()};
+        return rt_denoise(ctx, &p, &in, nullptr, frame) == RT_OK;
+    }
+};
+
+// --denoise without --progressive: one device, the whole frame: colours, guides, filter, BMP.
+int run_denoised(const Args& a, rt_scene* scene, uint32_t W, uint32_t H, uint32_t spp) {
+    uint32_t pitch = 0;
+    uint8_t hdr[122];
+    rt_bmp_header(hdr, W, H, &pitch);
+    rt_ctx* ctx = nullptr;
+    if (rt_ctx_create(0, &ctx) != RT_OK) { std::printf("error: %s\n", rt_last_error(nullptr)); return 1; }
+    auto done_with = [&](int code) {
+        rt_ctx_destroy(ctx);
+        return code;
+    };
+    if (rt_scene_upload(ctx, scene) != RT_OK) { std::printf("error: %s\n", rt_last_error(ctx)); return done_with(1); }
+    Denoiser dn;
+    if (!dn.setup(ctx, a, W, H, spp, pitch)) { std::printf("error: --denoise: %s\n", rt_last_error(ctx)); return done_with(2); }
+    rt_render_opts o;
+    rt_render_opts_default(&o, W, H);
+    o.max_depth = a.max_depth; o.spp = spp; o.algo = a.algo; o.jitter = a.jitter; o.seed = a.seed;
+    o.flags = RT_OUT_RGB_F32;
+    std::vector<float> rgb(static_cast<size_t>(W) * H * 3);
+    std::vector<uint8_t> frame(static_cast<size_t>(pitch) * H, 0);
+    rt_stats st{};
+    if (rt_render(ctx, &o, rgb.data(), nullptr, &st) != RT_OK) { std::printf("error: %s\n", rt_last_error(ctx)); return done_with(1); }
+    if (!dn.run(ctx, rgb.data(), frame.data())) { std::printf("error: --denoise: %s\n", rt_last_error(ctx)); return done_with(1); }
+    if (rt_write_bmp(a.out.c_str(), W, H, frame.data(), pitch) != RT_OK) {
+        std::printf("error: %s\n", rt_last_error(nullptr));
+        return done_with(1);
+    }
+    std::fprintf(stderr, "%ux%u spp=%u depth=%u gpus=1 denoise %ld (flags 0x%x): %llu rays, kernel %.3f ms\n", W, H, spp, a.max_depth,
+                 a.denoise, a.denoise_flags, static_cast<unsigned long long>(st.rays), st.kernel_ms);
+    return done_with(0);
 }
 
 // --progressive / --checkpoint: one device, the whole frame in one accumulator, `total` samples in steps.
@@ -141,6 +225,12 @@ int run_progressive(const Args& a, rt_scene* scene, const std::string& text, uin
             return done_with(1);
         }
     }
+    Denoiser dn;                       // --denoise: the guides once, at the frame's sample count
+    std::vector<float> rgb;
+    if (a.denoise > 0) {
+        if (!dn.setup(ctx, a, W, H, total, pitch)) { std::printf("error: --denoise: %s\n", rt_last_error(ctx)); return done_with(2); }
+        rgb.resize(n_doubles);
+    }
     const uint32_t step = a.progressive > 0 ? static_cast<uint32_t>(std::min<long>(a.progressive, total)) : total;
     std::vector<uint8_t> frame(static_cast<size_t>(pitch) * H, 0);
     const std::string tmp = a.out + ".tmp";
@@ -159,7 +249,8 @@ int run_progressive(const Args& a, rt_scene* scene, const std::string& text, uin
         kms += st.kernel_ms;
         if (done == 0) break;
         // the image of the samples so far, under a temporary name first: --out is always a whole image
-        if (rt_accum_resolve_host(ctx, acc, pitch, nullptr, frame.data()) != RT_OK) {
+        if (a.denoise > 0 ? rt_accum_resolve_host(ctx, acc, pitch, rgb.data(), nullptr) != RT_OK || !dn.run(ctx, rgb.data(), frame.data())
+                          : rt_accum_resolve_host(ctx, acc, pitch, nullptr, frame.data()) != RT_OK) {
             std::printf("error: %s\n", rt_last_error(ctx));
             return done_with(1);
         }
@@ -249,6 +340,24 @@ int main(int argc, char** argv) {
     int ndev = 0;
     rt_device_count(&ndev);
     if (ndev < 1) { std::printf("error: no GPU\n"); return 1; }
+    if (a.denoise != 0 || a.bad_denoise_flags) {
+        if (a.bad_denoise_flags) {
+            std::printf("error: --denoise-flags takes normal, depth, color, demodulate (comma-separated) or none\n");
+            return 2;
+        }
+        if (a.denoise < 1 || a.denoise > 8) { std::printf("error: --denoise takes 1..8 passes\n"); return 2; }
+        if (a.gpus > 1) {
+            std::printf("error: --denoise filters on one device: not with --gpus %d\n", a.gpus);
+            return 2;
+        }
+        if (!a.aov.empty()) { std::printf("error: --denoise filters the image: not with --aov\n"); return 2; }
+        if (spp == 0) { std::printf("error: --spp is 0 and the scene's antialias is 0\n"); return 1; }
+        if (a.progressive <= 0 && a.checkpoint.empty()) {
+            const int rc = run_denoised(a, scene, W, H, spp);
+            rt_scene_free(scene);
+            return rc;
+        }
+    }
     if (!a.aov.empty()) {
         if (a.gpus > 1) {
             std::printf("error: --aov renders on one device: not with --gpus %d\n", a.gpus);

@@ -3,6 +3,7 @@
 #include "render_plan.hpp"
 
 #include <algorithm>
+#include <cmath>
 
 namespace rtamd {
 
@@ -279,6 +280,47 @@ int plan_query_args(const QueryArgs& a, const char** err) {
 }
 
 uint32_t plan_query_workgroups(uint64_t n, int n_cu) { return plan_aov_workgroups(n, n_cu); }
+
+int plan_denoise_args(const rt_denoise_params* p, const rt_denoise_inputs* in, const void* out_rgb, const void* out_bgr,
+                      const char** err) {
+    auto refuse = [&](const char* why) {
+        *err = why;
+        return RT_E_INVALID;
+    };
+    auto sigma_ok = [](double v) { return std::isfinite(v) && v > 0.0; };
+    if (!p || !in) return refuse("rt_denoise: null argument");
+    if (p->width == 0 || p->height == 0) return refuse("rt_denoise: width and height must be > 0");
+    if (p->iterations < 1 || p->iterations > kDnMaxIterations) return refuse("rt_denoise: iterations must be 1..8");
+    if (p->flags & ~kDnAllFlags) return refuse("rt_denoise: unknown flag bits");
+    if (p->normal_squarings > kDnMaxSquarings) return refuse("rt_denoise: normal_squarings must be 0..10");
+    if (p->variant > 2) return refuse("rt_denoise: variant must be 0, 1 or 2");
+    if (!in->rgb) return refuse("rt_denoise: the rgb input is NULL");
+    if (((p->flags & RT_DN_NORMAL) && !in->normal) || ((p->flags & RT_DN_DEPTH) && !in->depth) ||
+        ((p->flags & RT_DN_DEMODULATE) && !in->albedo))
+        return refuse("rt_denoise: a selected guide's buffer is NULL");
+    if ((p->flags & RT_DN_DEPTH) && !sigma_ok(p->sigma_depth)) return refuse("rt_denoise: sigma_depth must be finite and > 0");
+    if ((p->flags & RT_DN_COLOR) && !sigma_ok(p->sigma_color)) return refuse("rt_denoise: sigma_color must be finite and > 0");
+    if (!out_rgb && !out_bgr) return refuse("rt_denoise: both outputs are NULL");
+    if (p->bgr_pitch != 0 && p->bgr_pitch / 3 < p->width) return refuse("rt_denoise: bgr_pitch is below 3 * width");
+    if (out_rgb == static_cast<const void*>(in->rgb)) return refuse("rt_denoise: out_rgb must not be the rgb input");
+    return RT_OK;
+}
+
+DenoisePlan plan_denoise(const rt_denoise_params& p) {
+    DenoisePlan d;
+    d.passes = p.iterations;
+    const uint32_t variant = p.variant ? p.variant : kDnAutoVariant;
+    d.variant = variant;
+    for (uint32_t i = 0; i < d.passes && i < kDnMaxIterations; ++i) {
+        d.step[i] = 1u << i;
+        d.lds[i] = variant == 2 && d.step[i] <= kDnLdsMaxStep;
+    }
+    d.grid_x = (p.width + kDnTileW - 1) / kDnTileW;
+    d.grid_y = (p.height + kDnTileH - 1) / kDnTileH;
+    d.image_bytes = align_up(static_cast<uint64_t>(p.width) * p.height * kDnRecordBytes, 256);
+    d.scratch_bytes = 3 * d.image_bytes;
+    return d;
+}
 
 StreamShape plan_streams(const SceneFacts& sf, const int64_t* tune, int mode, int src, uint32_t max_depth) {
     StreamShape s;

@@ -151,6 +151,32 @@ int plan_query_args(const QueryArgs& a, const char** err);
 // CU (all resident); the workgroups stride over the rays beyond that.
 uint32_t plan_query_workgroups(uint64_t n, int n_cu);
 
+// ---- denoiser (rt_denoise / rt_denoise_device) ---------------------------------------------------
+// The call's argument checks that need no device, in the order include/raytrace_amd.h lists them; p and in are the
+// caller's structs (either may be null: refused).  RT_OK or RT_E_INVALID with its text in *err.
+constexpr uint32_t kDnAllFlags = RT_DN_NORMAL | RT_DN_DEPTH | RT_DN_COLOR | RT_DN_DEMODULATE;
+constexpr uint32_t kDnMaxIterations = 8, kDnMaxSquarings = 10;
+int plan_denoise_args(const rt_denoise_params* p, const rt_denoise_inputs* in, const void* out_rgb, const void* out_bgr,
+                      const char** err);
+// The passes of a checked call.  Pass i has step 2^i.  A pass whose step is 1 or 2 has the LDS form (wf_denoise.hip
+// stages the workgroup's kDnTileW x kDnTileH tile and a halo of 2 * step pixels, which fits its static LDS up to
+// step kDnLdsMaxStep); every later pass reads its taps through L2.  variant 1: every pass direct; 2: LDS where it
+// exists; 0: kDnAutoVariant, the one measured faster.  The last pass writes the caller's outputs.
+// Scratch: two colour images and one guide image of 16 B per pixel, each 256-byte aligned.
+constexpr uint32_t kDnTileW = 64, kDnTileH = 8, kDnLdsMaxStep = 2;
+constexpr uint32_t kDnAutoVariant = 2;
+constexpr uint64_t kDnRecordBytes = 16;
+struct DenoisePlan {
+    uint32_t passes = 0;
+    uint32_t step[kDnMaxIterations] = {};
+    bool lds[kDnMaxIterations] = {};
+    uint32_t variant = 1;             // what ran for the steps <= kDnLdsMaxStep (the verbose line's V)
+    uint32_t grid_x = 0, grid_y = 0;  // workgroups of a filter pass: one per tile
+    uint64_t image_bytes = 0;         // one scratch image, aligned
+    uint64_t scratch_bytes = 0;       // all three
+};
+DenoisePlan plan_denoise(const rt_denoise_params& p);
+
 // ---- streams ----------------------------------------------------------------------------
 struct StreamShape {
     bool split = false;     // shadow + shading kernels on b streams of their own

@@ -2,7 +2,8 @@
 // translation units that implement it share: rt_device.cpp (create / destroy, tuning, probes),
 // rt_scene_upload.cpp, rt_render.cpp (the render path, lanes, reserve, statistics), rt_accum.cpp
 // (progressive rendering: the accumulator and its calls), rt_aov.cpp (first-hit feature buffers: the entry
-// points' checks and the host variant), rt_query.cpp (ray queries: the same) and rt_copy.cpp (device -> host copies).
+// points' checks and the host variant), rt_query.cpp (ray queries: the same), rt_denoise.cpp (the denoiser: checks,
+// scratch, passes, host variant) and rt_copy.cpp (device -> host copies).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -177,6 +178,12 @@ struct rt_ctx {
     uint32_t sdma_avail = 0, sdma_pref = 0, sdma_turn = 0;
     static constexpr int kSdmaSignals = rtamd::kRing + kSpRanges + 1;
     hsa_signal_t sdma_sig[kSdmaSignals] = {};
+    // the denoiser's scratch (rt_denoise.cpp): two colour images and one guide image, grown on demand; dn_done: the
+    // end of the last denoise on its stream, which the next one waits for (the scratch is shared)
+    void* d_dn = nullptr;
+    size_t dn_cap = 0;
+    hipEvent_t dn_done = nullptr;
+    bool dn_pending = false;
     int64_t tune[rtamd::kTuneCount];
     std::string err;
     rt_ctx() {

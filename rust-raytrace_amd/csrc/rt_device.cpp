@@ -92,6 +92,9 @@ void rt_ctx_destroy(rt_ctx* c) {
     if (c->d_path) (void)hipFree(c->d_path);
     if (c->d_rgb) (void)hipFree(c->d_rgb);
     if (c->d_bgr) (void)hipFree(c->d_bgr);
+    if (c->dn_pending) (void)hipEventSynchronize(c->dn_done);   // a denoise on a caller's stream still reads the scratch
+    if (c->d_dn) (void)hipFree(c->d_dn);
+    if (c->dn_done) (void)hipEventDestroy(c->dn_done);
     drop_lanes(c);
     for (hipEvent_t e : c->tev) (void)hipEventDestroy(e);
     if (c->render_done) (void)hipEventDestroy(c->render_done);

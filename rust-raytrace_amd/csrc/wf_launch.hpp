@@ -57,8 +57,8 @@ hipError_t launch_compose(const DevScene& sc, const FrameParams& fp, const WfBuf
 // (upload_srgb_table runs them all).  The lists below name the units; wf_sequence.hip, which
 // holds launch_warmup and the real warm-up kernel, is in none of them.
 #define RT_NEAREST_UNITS(X) X(wf_nearest_flat) X(wf_nearest_bvh) X(wf_nearest_prefix) X(wf_nearest_q4)
-#define RT_WARM_UNITS(X) X(trace_mega) RT_NEAREST_UNITS(X) X(wf_shade) X(wf_tail) X(wf_fold) X(wf_output) X(probes) X(wf_aov) X(wf_query)
-#define RT_SRGB_UNITS(X) X(trace_mega) RT_NEAREST_UNITS(X) X(wf_tail) X(wf_fold) X(wf_output)
+#define RT_WARM_UNITS(X) X(trace_mega) RT_NEAREST_UNITS(X) X(wf_shade) X(wf_tail) X(wf_fold) X(wf_output) X(probes) X(wf_aov) X(wf_query) X(wf_denoise)
+#define RT_SRGB_UNITS(X) X(trace_mega) RT_NEAREST_UNITS(X) X(wf_tail) X(wf_fold) X(wf_output) X(wf_denoise)
 
 #define RT_UNIT_WARM(unit)                                  \
     namespace {                                             \

@@ -37,6 +37,7 @@ RT_ALGO_WAVEFRONT_AA = 6        # one wavefront pass per jittered AA sample
 RT_JITTER_CENTER, RT_JITTER_RANDOM = 0, 1
 RT_AOV_DEPTH, RT_AOV_NORMAL, RT_AOV_ALBEDO, RT_AOV_COVERAGE, RT_AOV_OBJECT = 1, 2, 4, 8, 16     # rt_aov
 RT_AOV_ALL = 31
+RT_DN_NORMAL, RT_DN_DEPTH, RT_DN_COLOR, RT_DN_DEMODULATE = 1, 2, 4, 8                      # rt_denoise_flags
 # rt_aov bit -> (rt_aov_buffers field, elements per pixel, dtype)
 AOV_CHANNELS = {RT_AOV_DEPTH: ("depth", 1, np.float32), RT_AOV_NORMAL: ("normal", 3, np.float32),
                 RT_AOV_ALBEDO: ("albedo", 3, np.float32), RT_AOV_COVERAGE: ("coverage", 1, np.float32),
@@ -108,6 +109,16 @@ class rt_hit_buffers(C.Structure):
     _fields_ = [("t", C.c_void_p), ("object", C.c_void_p), ("normal", C.c_void_p)]
 
 
+class rt_denoise_params(C.Structure):
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("iterations", C.c_uint32), ("flags", C.c_uint32),
+                ("normal_squarings", C.c_uint32), ("variant", C.c_uint32), ("bgr_pitch", C.c_uint32), ("_pad", C.c_uint32),
+                ("sigma_color", C.c_double), ("sigma_depth", C.c_double)]
+
+
+class rt_denoise_inputs(C.Structure):
+    _fields_ = [("rgb", C.c_void_p), ("normal", C.c_void_p), ("depth", C.c_void_p), ("albedo", C.c_void_p)]
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise ImportError(f"{LIB_PATH} is missing: run `make -C rust-raytrace_amd` "
@@ -148,6 +159,9 @@ def _load():
                                               C.c_uint32, C.c_void_p]),
         "rt_query_occluded_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32,
                                                C.c_void_p]),
+        "rt_denoise": (C.c_int, [C.c_void_p, P(rt_denoise_params), P(rt_denoise_inputs), C.c_void_p, C.c_void_p]),
+        "rt_denoise_device": (C.c_int, [C.c_void_p, P(rt_denoise_params), P(rt_denoise_inputs), C.c_void_p, C.c_void_p,
+                                        C.c_void_p]),
         "rt_accum_create": (C.c_int, [C.c_void_p, P(rt_render_opts), P(C.c_void_p)]),
         "rt_accum_destroy": (None, [C.c_void_p]),
         "rt_accum_samples": (C.c_int, [C.c_void_p, P(C.c_uint32)]),
@@ -391,6 +405,14 @@ def render_opts(width, height, **kw):
     return o
 
 
+def denoise_params(width, height, iterations=5, flags=RT_DN_NORMAL | RT_DN_DEPTH, normal_squarings=5, variant=0,
+                   bgr_pitch=0, sigma_color=1.0, sigma_depth=0.05):
+    """An rt_denoise_params; the defaults are the settings the denoiser was tried with."""
+    return rt_denoise_params(width=width, height=height, iterations=iterations, flags=flags,
+                             normal_squarings=normal_squarings, variant=variant, bgr_pitch=bgr_pitch, _pad=0,
+                             sigma_color=sigma_color, sigma_depth=sigma_depth)
+
+
 def sources_id():
     """16 hex digits identifying the native sources (csrc/ and include/) this
     checkout builds: ties committed profile figures (profiles/pmc_traffic.json)
@@ -584,6 +606,40 @@ class Context:
         _check(lib.rt_query_occluded_device(self._h, C.c_void_p(d_rays_ptr or 0), C.c_void_p(d_r2_ptr or 0), int(n),
                                             C.c_void_p(d_occluded_ptr or 0), int(flags), C.c_void_p(stream_ptr or 0)),
                self._h)
+
+    def denoise(self, rgb, guides=None, rgb_out=True, bgr_out=True, **params):
+        """rt_denoise: the edge-avoiding a-trous filter on host arrays (synchronous) -> (rgb float32 [h, w, 3] or None,
+        bgr uint8 [h, pitch] or None).  rgb: float32 [h, w, 3]; guides: {"normal": [h, w, 3], "depth": [h, w],
+        "albedo": [h, w, 3]} float32, those the flags select; params: denoise_params' keywords."""
+        rgb = np.ascontiguousarray(rgb, dtype=np.float32)
+        h, w = rgb.shape[:2]
+        p = denoise_params(w, h, **params)
+        keep = [rgb]
+        ins = rt_denoise_inputs(rgb=rgb.ctypes.data)
+        for name, a in (guides or {}).items():
+            if name not in ("normal", "depth", "albedo"):
+                raise TypeError(f"unknown guide {name}")
+            a = np.ascontiguousarray(a, dtype=np.float32)
+            assert a.size == h * w * (1 if name == "depth" else 3), name
+            keep.append(a)
+            setattr(ins, name, a.ctypes.data)
+        pitch = p.bgr_pitch or 3 * w
+        out_rgb = np.zeros((h, w, 3), np.float32) if rgb_out else None
+        out_bgr = np.full((h, pitch), 0xCD, np.uint8) if bgr_out else None
+        _check(lib.rt_denoise(self._h, C.byref(p), C.byref(ins), out_rgb.ctypes.data if rgb_out else None,
+                              out_bgr.ctypes.data if bgr_out else None), self._h)
+        return out_rgb, out_bgr
+
+    def denoise_device(self, params, d_rgb_ptr, guide_ptrs, d_out_rgb_ptr, d_out_bgr_ptr, stream_ptr=None):
+        """rt_denoise_device: asynchronous, on device buffers (raw pointers, e.g. torch tensor.data_ptr()).  params:
+        denoise_params(..); guide_ptrs: {"normal" / "depth" / "albedo": pointer}."""
+        ins = rt_denoise_inputs(rgb=d_rgb_ptr or None)
+        for name, ptr in (guide_ptrs or {}).items():
+            if name not in ("normal", "depth", "albedo"):
+                raise TypeError(f"unknown guide {name}")
+            setattr(ins, name, ptr or None)
+        _check(lib.rt_denoise_device(self._h, C.byref(params), C.byref(ins), C.c_void_p(d_out_rgb_ptr or 0),
+                                     C.c_void_p(d_out_bgr_ptr or 0), C.c_void_p(stream_ptr or 0)), self._h)
 
     def reserve(self, opts, host=False, stream_ptr=None):
         """rt_ctx_reserve: allocate and warm up everything a render with opts needs (host: rt_render's
