@@ -81,7 +81,7 @@ static void rng_seed(rng_t* r, uint64_t seed) {
 }
 
 /* ---- keyed counter-based RNG (REF_RNG_KEYED): the specification shared with
- * the device path (trace_common.hpp).  A draw is a pure function of a 64-bit
+ * the device path (trace_rng.hpp).  A draw is a pure function of a 64-bit
  * key and a draw id; keys follow the recursion:
  *   pixel      kp = mix(mix(seed) + (y << 32 | x))         (frame coordinates)
  *   AA sample  ka = child(kp, aa)      jitter: jx = f64(ka, 0), jy = f64(ka, 1)

@@ -92,7 +92,7 @@ enum { REF_JITTER_CENTER = 0, REF_JITTER_RANDOM = 1 };
  * OS entropy, main.rs:43, so only its distribution is reproducible).  KEYED:
  * a counter-based stream keyed on the draw's place in the recursion (pixel,
  * AA sample, camera sample, path through the ray tree, draw id) -- the same
- * specification the device path implements (trace_common.hpp "keyed RNG"),
+ * specification the device path implements (trace_rng.hpp "keyed RNG"),
  * so device and oracle agree draw for draw, in any traversal order. */
 enum { REF_RNG_XORSHIFT = 0, REF_RNG_KEYED = 1 };
 

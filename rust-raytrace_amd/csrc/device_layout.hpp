@@ -176,7 +176,7 @@ struct DevScene {
     int32_t needs_path;             // a class only the path kernel implements (IndirectPhong, Transparent,
                                     // AreaLight, DepthOfFieldCamera)
     int32_t skybox;                 // SkyboxBackground (raytrace.rs:234-256): every schedule samples it for a ray
-                                    // that misses (trace_common.hpp background(); chain schedules: DESIGN.md §3.13)
+                                    // that misses (trace_frame.hpp background(); chain schedules: DESIGN.md §3.13)
     const uint8_t* tex;             // skybox texels
     const double* srgb_values;      // color.rs SRGB_VALUES (Color::from_srgb, color.rs:611-613)
     DevTexFace faces[6];            // px, nx, py, ny, pz, nz

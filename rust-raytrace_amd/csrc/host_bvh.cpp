@@ -6,7 +6,7 @@
 // conservative ("BVH exactness").  Conservative here:
 //   * each sphere's box is [c - r, c + r] widened by `pad` and rounded OUTWARD
 //     to f32 (so it contains every point the f64 test can report as a hit);
-//   * the traversal (trace_common.hpp, box_hit) widens every slab interval by
+//   * the traversal (trace_bvh.hpp, box_hit) widens every slab interval by
 //     a relative 1e-5, covering f32 rounding of the ray and of the slab math.
 // Binned SAH (16 bins) with leaves of <= 4 spheres; median split below depth
 // 40 keeps the depth (and the per-lane traversal stack) bounded.

@@ -269,7 +269,7 @@ LightGridResult build_view_grid(const std::vector<DevSphere>& spheres, const std
 }
 
 // The device's candidate list for a shadow query from p toward light `li`
-// (occluded_lgrid, trace_common.hpp), with the same f32 arithmetic: the always
+// (occluded_lgrid, trace_grid.hpp), with the same f32 arithmetic: the always
 // list, then p's cell up to the early stop.  Returns false when the device
 // would test every sphere (degenerate direction, or p beyond the culling domain
 // `reach`, DevScene::cull_reach) or the light has no grid.

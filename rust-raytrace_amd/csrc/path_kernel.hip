@@ -17,9 +17,9 @@
 // child by child), and the parent spawns its next child or returns.  The
 // stack lives in HBM, SoA per depth, so the lanes of a wave at the same depth
 // read and write consecutive words.  Queries go through the sphere BVH (exact
-// f64 leaf tests, trace_common.hpp), staged in LDS when it fits.
+// f64 leaf tests, trace_bvh.hpp), staged in LDS when it fits.
 //
-// Every random draw is keyed on its place in the recursion (trace_common.hpp
+// Every random draw is keyed on its place in the recursion (trace_rng.hpp
 // "keyed RNG"), so the image does not depend on the schedule and the oracle's
 // REF_RNG_KEYED mode reproduces it draw for draw.
 #include <hip/hip_runtime.h>

@@ -4,6 +4,7 @@
 // render_aov; the kernel wf_aov.hip's).
 #include <cstdio>
 
+#include "host_staging.hpp"
 #include "rt_ctx.hpp"
 
 using namespace rtamd;
@@ -42,38 +43,22 @@ int aov_device(rt_ctx* c, const rt_render_opts* o, uint32_t channels, const rt_a
 }
 
 // The host variant, the plain way: device buffers for the selected channels, the render on the context's
-// stream, one copy per channel, free.  No performance claim.
+// stream, one copy per channel, free (host_staging.hpp).
 int aov_host(rt_ctx* c, const rt_render_opts* o, uint32_t channels, const rt_aov_buffers* host, rt_stats* stats) {
     if (const int rc = check_call(c, o, channels, host); rc != RT_OK) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
     const uint64_t npix = static_cast<uint64_t>(o->tile_w) * o->tile_h;
-    void* const dst[5] = {host->depth, host->normal, host->albedo, host->coverage, host->object};
-    void* d[5] = {};
-    auto release = [&] {
-        for (void* p : d)
-            if (p) (void)hipFree(p);
-    };
-    for (int i = 0; i < 5; ++i) {
-        if (!((channels >> i) & 1u) || npix == 0) continue;
-        const hipError_t e = hipMalloc(&d[i], npix * kElems[i] * 4);
-        if (e != hipSuccess) {
-            release();
-            (void)hipGetLastError();
-            return e == hipErrorOutOfMemory ? fail(c, RT_E_NOMEM, "rt_render_aov: the device buffers do not fit") : hip_fail(c, e, "rt_render_aov");
-        }
-    }
     // (an empty tile has no buffers: the render checks the geometry and launches nothing)
-    AovOut out{static_cast<float*>(d[0]), static_cast<float*>(d[1]), static_cast<float*>(d[2]), static_cast<float*>(d[3]),
-               static_cast<int32_t*>(d[4])};
-    int rc = render_aov(c, o, out, channels, nullptr);
-    hipError_t e = hipSuccess;
-    for (int i = 0; i < 5 && rc == RT_OK && e == hipSuccess; ++i)
-        if (d[i]) e = hipMemcpyAsync(dst[i], d[i], npix * kElems[i] * 4, hipMemcpyDeviceToHost, c->stream);
-    const hipError_t es = hipStreamSynchronize(c->stream);      // also before the buffers are freed after a failure
-    release();
+    size_t bytes[5];
+    for (int i = 0; i < 5; ++i) bytes[i] = (channels >> i) & 1u ? npix * kElems[i] * 4 : 0;
+    const void* const in[5] = {};
+    void* const dst[5] = {host->depth, host->normal, host->albedo, host->coverage, host->object};
+    const StagedTexts texts{"rt_render_aov", "rt_render_aov: copy to the host", "rt_render_aov: synchronize"};
+    const int rc = run_staged(c, bytes, in, dst, texts, [&](const Staged<5>& s) {
+        const AovOut out{s.as<float>(0), s.as<float>(1), s.as<float>(2), s.as<float>(3), s.as<int32_t>(4)};
+        return render_aov(c, o, out, channels, nullptr);
+    });
     if (rc != RT_OK) return rc;
-    if (e != hipSuccess) return hip_fail(c, e, "rt_render_aov: copy to the host");
-    if (es != hipSuccess) return hip_fail(c, es, "rt_render_aov: synchronize");
     if (stats) return rt_ctx_stats(c, stats);
     return check_join_error(c);
 }

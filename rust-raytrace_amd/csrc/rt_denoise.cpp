@@ -4,6 +4,7 @@
 // A denoise is not a render: it needs no scene and touches neither the counters nor the last render's statistics.
 #include <cstdio>
 
+#include "host_staging.hpp"
 #include "rt_ctx.hpp"
 
 using namespace rtamd;
@@ -69,52 +70,27 @@ int denoise_device(rt_ctx* c, const rt_denoise_params* p, const rt_denoise_input
 
 // The host variant, the plain way: device buffers for the inputs the flags select and for the outputs asked for, the
 // filter on the context's stream, the copies back, free.  The BGR rows go through a tight device image, so that the
-// caller's padding bytes are never written.  No performance claim.
+// caller's padding bytes are never written: that copy is pitched, and follows the filter here (host_staging.hpp has
+// the rest).
 int denoise_host(rt_ctx* c, const rt_denoise_params* p, const rt_denoise_inputs* host, float* out_rgb, uint8_t* out_bgr) {
     if (const int rc = check_call(c, p, host, out_rgb, out_bgr); rc != RT_OK) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
-    const size_t npix = static_cast<size_t>(p->width) * p->height;
-    const bool use[4] = {true, (p->flags & RT_DN_NORMAL) != 0, (p->flags & RT_DN_DEPTH) != 0, (p->flags & RT_DN_DEMODULATE) != 0};
-    const float* const src[4] = {host->rgb, host->normal, host->depth, host->albedo};
-    const size_t bytes[6] = {npix * 12, npix * 12, npix * 4, npix * 12, out_rgb ? npix * 12 : 0, out_bgr ? npix * 3 : 0};
-    void* d[6] = {};
-    auto release = [&] {
-        for (void* q : d)
-            if (q) (void)hipFree(q);
-    };
-    for (int i = 0; i < 6; ++i) {
-        if ((i < 4 && !use[i]) || bytes[i] == 0) continue;
-        const hipError_t e = hipMalloc(&d[i], bytes[i]);
-        if (e != hipSuccess) {
-            d[i] = nullptr;
-            release();
-            (void)hipGetLastError();
-            return e == hipErrorOutOfMemory ? fail(c, RT_E_NOMEM, "rt_denoise: the device buffers do not fit") : hip_fail(c, e, "rt_denoise");
-        }
-    }
-    hipError_t e = hipSuccess;
-    for (int i = 0; i < 4 && e == hipSuccess; ++i)
-        if (d[i]) e = hipMemcpyAsync(d[i], src[i], bytes[i], hipMemcpyHostToDevice, c->stream);
-    int rc = RT_OK;
-    if (e == hipSuccess) {
+    const size_t npix = static_cast<size_t>(p->width) * p->height, row = 3 * static_cast<size_t>(p->width);
+    const size_t bytes[6] = {npix * 12, p->flags & RT_DN_NORMAL ? npix * 12 : 0, p->flags & RT_DN_DEPTH ? npix * 4 : 0,
+                             p->flags & RT_DN_DEMODULATE ? npix * 12 : 0, out_rgb ? npix * 12 : 0, out_bgr ? npix * 3 : 0};
+    const void* const in[6] = {host->rgb, host->normal, host->depth, host->albedo, nullptr, nullptr};
+    void* const out[6] = {nullptr, nullptr, nullptr, nullptr, out_rgb, nullptr};
+    const StagedTexts texts{"rt_denoise", "rt_denoise: copy", "rt_denoise: synchronize"};
+    return run_staged(c, bytes, in, out, texts, [&](const Staged<6>& s) -> int {
         rt_denoise_params q = *p;
         q.bgr_pitch = 0;
-        const rt_denoise_inputs dev{static_cast<const float*>(d[0]), static_cast<const float*>(d[1]), static_cast<const float*>(d[2]),
-                                    static_cast<const float*>(d[3])};
-        rc = denoise_device(c, &q, &dev, static_cast<float*>(d[4]), static_cast<uint8_t*>(d[5]), nullptr);
-    }
-    if (rc == RT_OK && e == hipSuccess && d[4]) e = hipMemcpyAsync(out_rgb, d[4], bytes[4], hipMemcpyDeviceToHost, c->stream);
-    if (rc == RT_OK && e == hipSuccess && d[5]) {
-        const size_t pitch = p->bgr_pitch ? p->bgr_pitch : 3 * static_cast<size_t>(p->width);
-        e = hipMemcpy2DAsync(out_bgr, pitch, d[5], 3 * static_cast<size_t>(p->width), 3 * static_cast<size_t>(p->width), p->height,
-                             hipMemcpyDeviceToHost, c->stream);
-    }
-    const hipError_t es = hipStreamSynchronize(c->stream);      // also before the buffers are freed after a failure
-    release();
-    if (rc != RT_OK) return rc;
-    if (e != hipSuccess) return hip_fail(c, e, "rt_denoise: copy");
-    if (es != hipSuccess) return hip_fail(c, es, "rt_denoise: synchronize");
-    return RT_OK;
+        const rt_denoise_inputs dev{s.as<const float>(0), s.as<const float>(1), s.as<const float>(2), s.as<const float>(3)};
+        if (const int rc = denoise_device(c, &q, &dev, s.as<float>(4), s.as<uint8_t>(5), nullptr); rc != RT_OK) return rc;
+        if (!s.d[5]) return RT_OK;
+        const hipError_t e = hipMemcpy2DAsync(out_bgr, p->bgr_pitch ? p->bgr_pitch : row, s.d[5], row, row, p->height,
+                                              hipMemcpyDeviceToHost, c->stream);
+        return e == hipSuccess ? RT_OK : hip_fail(c, e, texts.copy);
+    });
 }
 
 }  // namespace

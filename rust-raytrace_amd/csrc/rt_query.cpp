@@ -4,6 +4,7 @@
 // the kernels wf_query.hip's).
 #include <cstdio>
 
+#include "host_staging.hpp"
 #include "rt_ctx.hpp"
 
 using namespace rtamd;
@@ -54,48 +55,11 @@ int occluded_device(rt_ctx* c, const double* d_rays, const double* d_r2, uint32_
     return render_query(c, q, stream);
 }
 
-// The host variants, the plain way: device buffers for the rays, the ranges and the selected outputs, one copy in,
-// the render on the context's stream, one copy per output, free.  No performance claim.
-// Staged: the call's device buffers (rays, ranges or t, object, normal, occluded), bytes[i] each (0: none).
-struct Staged {
-    static constexpr int kN = 5;
-    void* d[kN] = {};
-    void release() {
-        for (void*& p : d)
-            if (p) { (void)hipFree(p); p = nullptr; }
-    }
-    int alloc(rt_ctx* c, const size_t bytes[kN], const char* who) {
-        for (int i = 0; i < kN; ++i) {
-            if (!bytes[i]) continue;
-            const hipError_t e = hipMalloc(&d[i], bytes[i]);
-            if (e != hipSuccess) {
-                d[i] = nullptr;
-                release();
-                (void)hipGetLastError();
-                return e == hipErrorOutOfMemory ? fail(c, RT_E_NOMEM, std::string(who) + ": the device buffers do not fit")
-                                                : hip_fail(c, e, who);
-            }
-        }
-        return RT_OK;
-    }
-};
-
-// Copies in (in[i]: the host source of buffer i, null: none), the render, copies out (out[i]: the host destination,
-// null: none), synchronise, free: on every path.
-int run_host(rt_ctx* c, Staged& s, const size_t bytes[Staged::kN], const void* const in[Staged::kN], void* const out[Staged::kN],
-             const QueryCall& q, rt_stats* stats, const char* who) {
-    hipError_t e = hipSuccess;
-    for (int i = 0; i < Staged::kN && e == hipSuccess; ++i)
-        if (s.d[i] && in[i]) e = hipMemcpyAsync(s.d[i], in[i], bytes[i], hipMemcpyHostToDevice, c->stream);
-    int rc = RT_OK;
-    if (e == hipSuccess) rc = render_query(c, q, nullptr);
-    for (int i = 0; i < Staged::kN && rc == RT_OK && e == hipSuccess; ++i)
-        if (s.d[i] && out[i]) e = hipMemcpyAsync(out[i], s.d[i], bytes[i], hipMemcpyDeviceToHost, c->stream);
-    const hipError_t es = hipStreamSynchronize(c->stream);      // also before the buffers are freed after a failure
-    s.release();
+// The host variants, the plain way (host_staging.hpp): device buffers for the rays, the ranges and the selected
+// outputs, one copy in, the render on the context's stream, one copy per output, free.  After a render that
+// succeeded: the statistics, if asked for, else what a device-side join may have to report.
+int after_render(rt_ctx* c, int rc, rt_stats* stats) {
     if (rc != RT_OK) return rc;
-    if (e != hipSuccess) return hip_fail(c, e, who);
-    if (es != hipSuccess) return hip_fail(c, es, who);
     if (stats) return rt_ctx_stats(c, stats);
     return check_join_error(c);
 }
@@ -106,15 +70,16 @@ int nearest_host(rt_ctx* c, const double* rays, uint32_t n, uint32_t channels, c
     HIP_TRY(c, hipSetDevice(c->device));
     const QueryOut sel = selected(n, channels, host);
     const size_t N = n;
-    const size_t bytes[Staged::kN] = {N * 48, sel.t ? N * 8 : 0, sel.object ? N * 4 : 0, sel.normal ? N * 24 : 0, 0};
-    const void* const in[Staged::kN] = {rays, nullptr, nullptr, nullptr, nullptr};
-    void* const out[Staged::kN] = {nullptr, sel.t, sel.object, sel.normal, nullptr};
-    Staged s;
-    if (const int rc = s.alloc(c, bytes, "rt_query_nearest"); rc != RT_OK) return rc;
-    QueryCall q;
-    q.rays = static_cast<const double*>(s.d[0]); q.n = n; q.channels = channels; q.flags = flags;
-    q.out = QueryOut{static_cast<double*>(s.d[1]), static_cast<int32_t*>(s.d[2]), static_cast<double*>(s.d[3])};
-    return run_host(c, s, bytes, in, out, q, stats, "rt_query_nearest");
+    const size_t bytes[4] = {N * 48, sel.t ? N * 8 : 0, sel.object ? N * 4 : 0, sel.normal ? N * 24 : 0};
+    const void* const in[4] = {rays, nullptr, nullptr, nullptr};
+    void* const out[4] = {nullptr, sel.t, sel.object, sel.normal};
+    const char* const who = "rt_query_nearest";
+    return after_render(c, run_staged(c, bytes, in, out, StagedTexts{who, who, who}, [&](const Staged<4>& s) {
+        QueryCall q;
+        q.rays = s.as<const double>(0); q.n = n; q.channels = channels; q.flags = flags;
+        q.out = QueryOut{s.as<double>(1), s.as<int32_t>(2), s.as<double>(3)};
+        return render_query(c, q, nullptr);
+    }), stats);
 }
 
 int occluded_host(rt_ctx* c, const double* rays, const double* r2, uint32_t n, uint8_t* occluded, uint32_t flags,
@@ -122,17 +87,17 @@ int occluded_host(rt_ctx* c, const double* rays, const double* r2, uint32_t n, u
     if (const int rc = check_call(c, true, false, rays, n, 0, nullptr, occluded, flags); rc != RT_OK) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
     const size_t N = n;
-    const size_t bytes[Staged::kN] = {N * 48, r2 ? N * 8 : 0, 0, 0, N};
-    const void* const in[Staged::kN] = {rays, r2, nullptr, nullptr, nullptr};
-    void* const out[Staged::kN] = {nullptr, nullptr, nullptr, nullptr, n ? occluded : nullptr};
-    Staged s;
-    if (const int rc = s.alloc(c, bytes, "rt_query_occluded"); rc != RT_OK) return rc;
-    QueryCall q;
-    q.occlusion = true;
-    q.rays = static_cast<const double*>(s.d[0]); q.r2 = static_cast<const double*>(s.d[1]); q.ranged = r2 != nullptr;
-    q.n = n; q.flags = flags;
-    q.occluded = static_cast<uint8_t*>(s.d[4]);
-    return run_host(c, s, bytes, in, out, q, stats, "rt_query_occluded");
+    const size_t bytes[3] = {N * 48, r2 ? N * 8 : 0, N};
+    const void* const in[3] = {rays, r2, nullptr};
+    void* const out[3] = {nullptr, nullptr, n ? occluded : nullptr};
+    const char* const who = "rt_query_occluded";
+    return after_render(c, run_staged(c, bytes, in, out, StagedTexts{who, who, who}, [&](const Staged<3>& s) {
+        QueryCall q;
+        q.occlusion = true;
+        q.rays = s.as<const double>(0); q.r2 = s.as<const double>(1); q.ranged = r2 != nullptr; q.n = n; q.flags = flags;
+        q.occluded = s.as<uint8_t>(2);
+        return render_query(c, q, nullptr);
+    }), stats);
 }
 
 }  // namespace

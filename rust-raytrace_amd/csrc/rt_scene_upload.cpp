@@ -287,13 +287,13 @@ static int scene_upload(rt_ctx* c, const rt_scene* s) {
         bvh.nodes.size() * sizeof(DevBvhNode) + spheres.size() * (sizeof(DevSphere) + 4) > kLdsBudget)
         bvh = build_sphere_bvh(sx, sy, sz, srad, pad, 4);
     const Bvh4Result bvh4 = collapse_bvh4(bvh);
-    // traversal stacks hold 64 entries (trace_common.hpp kBvhStack / kBvh4Stack)
+    // traversal stacks hold 64 entries (trace_bvh.hpp kBvhStack / kBvh4Stack)
     if (bvh_depth(bvh) > 64) return fail(c, RT_E_UNSUPPORTED, "sphere BVH deeper than the traversal stack");
     c->deep_bvh4 = bvh4_stack_need(bvh4) > 64;
-    // compact stack (trace_common.hpp kShortStack, stk_entry16): the stack never holds more
+    // compact stack (trace_bvh.hpp kShortStack, stk_entry16): the stack never holds more
     // entries than the deepest inner node's depth; node indices and leaf codes
     // (first << 3 | count - 1) must fit a signed 16-bit field; the whole-LDS walk stores inner
-    // nodes as byte offsets (c + 1) * 8 (trace_common.hpp node_byte_off)
+    // nodes as byte offsets (c + 1) * 8 (trace_view.hpp node_byte_off)
     c->short_stack = bvh_depth(bvh) <= 32 && bvh.nodes.size() < 4095 && spheres.size() <= 4096;
     c->short_stack18 = bvh_depth(bvh) <= 32 && bvh.nodes.size() < 131072 && spheres.size() <= 16383;
     // binary16 nodes only for trees that do not fit LDS whole (the prefix source reads them)

@@ -9,7 +9,7 @@
 //
 //  * wavefront (wf_*, wf_device.hpp): one generation per recursion depth, one small kernel per
 //    step of a generation.
-#define RT_UNIT trace_mega      // reads the sRGB table: its own copy (trace_common.hpp)
+#define RT_UNIT trace_mega      // reads the sRGB table: its own copy (trace_types.hpp)
 #include <hip/hip_runtime.h>
 
 #include <cstdint>

@@ -9,7 +9,7 @@
 //                kLast: the pass that remodulates and writes the caller's f32 and sRGB outputs row segment by row
 //                segment (store_row_segment, the staged sRGB table: what wf_compose and accum_resolve do).
 // No walk stack, no private arrays: no scratch.
-#define RT_UNIT wf_denoise      // reads the sRGB table: its own copy (trace_common.hpp)
+#define RT_UNIT wf_denoise      // reads the sRGB table: its own copy (trace_types.hpp)
 #include <hip/hip_runtime.h>
 
 #include <cstdint>

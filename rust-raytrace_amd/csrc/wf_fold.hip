@@ -1,6 +1,6 @@
 // The fold of the wavefront schedule: wf_fold (every ended chain's levels onto its terminal, and
 // its pixel) and, on a skybox scene, wf_sky_term before it.
-#define RT_UNIT wf_fold         // reads the sRGB table: its own copy (trace_common.hpp)
+#define RT_UNIT wf_fold         // reads the sRGB table: its own copy (trace_types.hpp)
 #include <hip/hip_runtime.h>
 
 #include <cstdint>

@@ -53,7 +53,7 @@ hipError_t launch_compose(const DevScene& sc, const FrameParams& fp, const WfBuf
 // Every translation unit with kernels is a code object of its own, loaded by its first launch:
 // RT_UNIT_WARM(unit) gives the unit an empty kernel and unit_warm_<unit>, which launches it
 // (launch_warmup runs them all).  RT_UNIT_SRGB(unit) gives a unit that reads c_srgb_avg (it
-// defines RT_UNIT for its copy, trace_common.hpp) the upload of that copy, unit_srgb_<unit>
+// defines RT_UNIT for its copy, trace_types.hpp) the upload of that copy, unit_srgb_<unit>
 // (upload_srgb_table runs them all).  The lists below name the units; wf_sequence.hip, which
 // holds launch_warmup and the real warm-up kernel, is in none of them.
 #define RT_NEAREST_UNITS(X) X(wf_nearest_flat) X(wf_nearest_bvh) X(wf_nearest_prefix) X(wf_nearest_q4)

@@ -1,6 +1,6 @@
 // The kernels that write pixels and statistics outside the fold: the row-by-row compose and
 // resolve passes, a skybox scene's camera misses, the sparse-copy kernels and the tally.
-#define RT_UNIT wf_output       // reads the sRGB table: its own copy (trace_common.hpp)
+#define RT_UNIT wf_output       // reads the sRGB table: its own copy (trace_types.hpp)
 #include <hip/hip_runtime.h>
 
 #include <algorithm>

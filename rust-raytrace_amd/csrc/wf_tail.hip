@@ -1,6 +1,6 @@
 // The fused tail of the wavefront schedule: one launch that takes every chain still running at
 // generation T-1 through all its remaining bounces and folds it (wf_tail).
-#define RT_UNIT wf_tail         // reads the sRGB table: its own copy (trace_common.hpp)
+#define RT_UNIT wf_tail         // reads the sRGB table: its own copy (trace_types.hpp)
 #include <hip/hip_runtime.h>
 
 #include <cstdint>

@@ -3,7 +3,7 @@ oracle's exported building blocks only -- a helper of test_aov_model.py (which p
 oracle's renders) and test_gpu_aov.py (which compares the device with it, bit for bit).
 
   camera       ref64.camera_build (camera.rs:51-73) gives position and matrix
-  keys         kmix / key_child / key_pixel / key_f64 of trace_common.hpp "keyed RNG", here in
+  keys         kmix / key_child / key_pixel / key_f64 of trace_rng.hpp "keyed RNG", here in
                64-bit-masked Python ints and Python floats
   pixel -> ray main.rs:39-41, 50-53, then matrix * (px, py, 1) and v / sqrt(sqnorm) per component
                (camera.rs:78), in Python floats
@@ -36,7 +36,7 @@ CASES = [(1, CENTER), (3, CENTER), (4, RANDOM)]        # (spp, jitter) every sce
 SEEDS = (7, 0x5EED5EED5EED)
 
 
-# ---- keyed RNG (trace_common.hpp) ------------------------------------------------------------
+# ---- keyed RNG (trace_rng.hpp) ---------------------------------------------------------------
 def kmix(z):
     z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & M64
     z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & M64

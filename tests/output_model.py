@@ -39,7 +39,7 @@ def quantise(v):
 
 
 def binary_search(v, turns=8, guard=True, guard_ge=False):
-    """The device's form of the quantiser (trace_common.hpp to_srgb) restated: the guard `!(v < T_254)` (or,
+    """The device's form of the quantiser (trace_types.hpp to_srgb) restated: the guard `!(v < T_254)` (or,
     guard_ge, the edit `v >= T_254`, which lets NaN through), then `turns` halvings of [0, 254].  For the CPU
     module: which edits of that function change its result at all."""
     v = np.asarray(v, np.float64).reshape(-1)

@@ -146,6 +146,17 @@ def test_one_output_at_a_time(gpu_ctx, images):
     same(None, bgr, model, "bgr only")
 
 
+def test_bgr_alone_into_padded_rows(gpu_ctx):
+    """The host variant's pitched copy with no f32 output beside it: the model's bytes, and the padding untouched."""
+    for (w, h), pad in (((8, 6), 5), ((5, 3), 1)):
+        img = dm.random_image(h, w, 11)
+        kw = dict(SETTINGS, iterations=2, flags=15, bgr_pitch=3 * w + pad)
+        none, bgr = gpu_ctx.denoise(img[0], guides_of(img), rgb_out=False, **kw)
+        assert none is None and bgr.shape == (h, 3 * w + pad)
+        same(None, bgr, dm.denoise(*img, **kw), ("bgr only, padded", w, h))
+        assert (bgr[:, 3 * w:] == 0xCD).all()
+
+
 def test_needs_no_scene_and_leaves_the_statistics_alone(gpu_ctx, images):
     img = images[(37, 29, False)]
     with lr.Context(0) as fresh:                              # nothing uploaded

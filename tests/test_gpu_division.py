@@ -2,7 +2,7 @@
 computes it: sphere_k's per-ray reciprocal of 2a (v_rcp_f64 + two Newton steps)
 finished per sphere by div_a2 with the division's own correction steps inside
 an exponent window, the compiler's full f64 division outside it
-(trace_common.hpp; DESIGN.md §4 "Division by 2a").  The claim is that this is
+(trace_prims.hpp; DESIGN.md §4 "Division by 2a").  The claim is that this is
 the correctly rounded quotient bit for bit; here it is checked directly,
 through rt_div_a2_check, against the device's own division and numpy's
 (IEEE) division on > 10^7 operand pairs: random operands, both edges of the
@@ -73,7 +73,7 @@ def test_sphere_sqrt_is_ieee_bit_for_bit(gpu_ctx):
     """The sphere test's square root (shapes.rs:67) as sphere_roots computes it:
     sqrt_win, the compiler's f64 sqrt sequence without its scaling of operands
     below 2^-767 (and its +-0 / +inf fixup), inside [2^-767, +inf), the full
-    sqrt outside (trace_common.hpp).  Against the device's own
+    sqrt outside (trace_prims.hpp).  Against the device's own
     sqrt and numpy's (IEEE) on > 10^7 operands: every exponent, both edges of
     the window and just outside, denormals, +-0, infinities, NaNs, negatives."""
     rng = np.random.default_rng(20261018)

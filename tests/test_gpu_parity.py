@@ -144,7 +144,7 @@ def test_directional_lights_and_parallel_planes(gpu_ctx):
 @pytest.mark.parametrize("algo", [lr.RT_ALGO_WAVEFRONT, lr.RT_ALGO_WAVEFRONT_BRUTE, lr.RT_ALGO_BRUTE_LDS])
 def test_extreme_light_and_plane_magnitudes(gpu_ctx, algo):
     """Operands outside the window of the sphere test's hoisted division
-    (trace_common.hpp div_a2: 2a in [2^-100, 2^101)): a directional light of
+    (trace_prims.hpp div_a2: 2a in [2^-100, 2^101)): a directional light of
     magnitude 1e-35 (its shadow rays keep the unnormalised -direction, a = 1e-70),
     one of magnitude 1e34, and mirror planes with normals of length 1e25 and 1e-20
     (reflection directions d - 2n(d.n) far from unit length), over random spheres:
@@ -312,7 +312,7 @@ def test_fused_tail_matches_oracle(gpu_ctx, scene):
 
 @pytest.mark.parametrize("scene", ["axis_ties", "config3", "dense", "planes_nan", "config4", "camera_inside"])
 def test_camera_view_grid_matches_oracle(gpu_ctx, scene):
-    """Generation 0 through the camera's view grid (tuning cam 3, trace_common.hpp
+    """Generation 0 through the camera's view grid (tuning cam 3, trace_grid.hpp
     nearest_cgrid; spheres in LDS, or through L2 for 10k spheres): camera rays
     on the axes, coincident spheres, NaN planes, the camera inside spheres and
     the C3 / C4 workloads match the oracle bit for bit."""
@@ -480,7 +480,7 @@ def test_half_node_prefix_source_is_bit_identical(gpu_ctx):
 
 @pytest.mark.parametrize("scene", ["axis_ties", "sphere_chain", "config3", "planes_nan", "extreme", "config4"])
 def test_quantised_tree_matches_oracle(gpu_ctx, scene):
-    """The quantised 4-wide tree (trace_common.hpp nearest_q4; host_bvh.cpp
+    """The quantised 4-wide tree (trace_bvh4.hpp nearest_q4; host_bvh.cpp
     quantize_bvh4) forced onto every nearest-hit generation: whole in LDS (src
     25) and with a 1 KB LDS prefix, every other node read through L2 (src 26).
     Ties across leaves, axis-aligned rays, the deepest small tree, NaN planes,

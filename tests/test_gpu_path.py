@@ -3,7 +3,7 @@
 The path kernel carries the classes the wavefront chain does not: IndirectPhong
 and Transparent materials, AreaLight, DepthOfFieldCamera and random AA jitter
 with several samples per pixel.  Random draws are keyed on their place in the
-recursion (trace_common.hpp "keyed RNG"); the oracle's REF_RNG_KEYED mode
+recursion (trace_rng.hpp "keyed RNG"); the oracle's REF_RNG_KEYED mode
 draws the same numbers, so:
   * scenes whose random draws feed only + - * / sqrt (random jitter, AreaLight,
     Transparent, Phong, Fresnel) must match BIT FOR BIT: BGR bytes equal, f32

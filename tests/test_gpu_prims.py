@@ -1,5 +1,5 @@
 """The sphere test, the plane test and the shading arithmetic on the device, record by record
-(rt_isect_check, rt_shade_check: probes.hip calls the functions of trace_common.hpp that the render kernels
+(rt_isect_check, rt_shade_check: probes.hip calls the functions of trace_prims.hpp and trace_shade.hpp that the render kernels
 call), bit for bit against prim_model.py, which test_prim_model.py pins to the oracle on the CPU; and the
 device's pow, sin and cos, measured against the host libm and against correctly rounded values
 (tests/golden/libm_cr.npz).  DESIGN.md §4 "Primitive probes".
