@@ -71,6 +71,9 @@ extern "C" {
  * or reads; RT_KF_COUNT is still 8.  A caller that needs them looks the symbols up.
  * Still 10: the denoiser (enum rt_denoise_flags, rt_denoise_params, rt_denoise_inputs, rt_denoise and
  * rt_denoise_device) adds functions, one enum and two structs in the same way; no tuning key.
+ * Still 10: second moments (rt_accum_create_moments, rt_accum_has_moments, rt_accum_download_moments /
+ * upload_moments, rt_accum_noise / noise_host, rt_checkpoint_write_moments / read_moments) add functions only:
+ * no struct, enum or tuning key; accum_noise is timed under RT_KF_COMPOSE.
  * 9: first-hit feature buffers: enum rt_aov, rt_aov_buffers, rt_render_aov and rt_render_aov_device
  * (depth, normal, albedo, coverage and object id of the camera rays' first hits).  Functions and types
  * added only: no struct, enum value or tuning key changed, RT_KF_COUNT is still 8.
@@ -589,6 +592,53 @@ int rt_accum_upload(rt_ctx* ctx, rt_accum* acc, const double* sums, size_t n_dou
  * that would overflow.  Nothing of the file is trusted before it is checked. */
 int rt_checkpoint_write(const char* path, const rt_render_opts* opts, uint64_t scene_hash, uint32_t samples, const double* sums, size_t n_doubles);
 int rt_checkpoint_read(const char* path, rt_render_opts* opts, uint64_t* scene_hash, uint32_t* samples, double* sums, size_t cap_doubles);
+
+/* ---- second moments: per-pixel variance and a noise count ------------------------------
+ * A moments accumulator keeps, beside the sum S_c of every pixel and channel, the sum of squares Q_c (48 B
+ * per pixel; the squares are a plane of their own after the tile's sums, both allocated at creation).  It is an
+ * rt_accum in every other respect: rt_render_accumulate, rt_accum_resolve / resolve_host, rt_accum_download,
+ * rt_accum_reset, rt_accum_samples and rt_accum_destroy take both kinds, S has the bits a plain accumulator has,
+ * and the call's rays, shadow rays and statistics are the plain call's.  ABI version, structs, enums and
+ * RT_KF_COUNT are unchanged: these are new functions only.
+ *
+ * The rule.  All arithmetic is f64; every operation written below is ONE IEEE operation: a product and the
+ * sum or difference that follows it are two roundings, never an fma.
+ *   Moments.  Sample k contributes q = s_c * s_c, s being the value added to S_c.  Sample 0 stores 0.0 + q
+ *   without reading Q (stale memory is never read; rt_accum_reset clears nothing); sample k > 0 loads Q, adds q
+ *   and stores.  A call never sums its own squares among themselves first, so Q, like S, does not depend on how
+ *   the samples were split over calls or algorithms.  NaN and +-inf propagate as IEEE gives them.
+ *   Estimate, for n = samples >= 2, N = (double)n:
+ *     mean_c = S_c / N;  d_c = Q_c - (S_c * mean_c);
+ *     v_c = (d_c < 0.0) ? 0.0 : d_c / (N * (N - 1.0))        (a NaN d_c stays NaN): the variance of the mean;
+ *     err = sqrt((v_r + v_g) + v_b) / (floor + ((|mean_r| + |mean_g|) + |mean_b|));
+ *     a pixel is above when !(err <= threshold), on the f64 value: a NaN err is above.
+ *   variance: f32 [tile_h, tile_w, 3] = (float)v_c; error: f32 [tile_h, tile_w] = (float)err; above: the number
+ *   of pixels above (an integer: independent of the order the device counts in). */
+int rt_accum_create_moments(rt_ctx* ctx, const rt_render_opts* opts, rt_accum** out);   /* as rt_accum_create */
+int rt_accum_has_moments(const rt_accum* acc, int32_t* flag);                            /* 1 or 0 */
+/* rt_accum_upload on a moments accumulator -> RT_E_INVALID (it would leave Q stale).  These two move Q (3 * tile_w
+ * * tile_h doubles; of no samples: zeros) and, uploading, replace sums, squares and count together; on a plain
+ * accumulator -> RT_E_INVALID.  Synchronous, as rt_accum_download / upload. */
+int rt_accum_download_moments(rt_ctx* ctx, rt_accum* acc, double* squares, size_t cap_doubles);
+int rt_accum_upload_moments(rt_ctx* ctx, rt_accum* acc, const double* sums, const double* squares, size_t n_doubles, uint32_t samples);
+/* The estimate.  d_variance / d_error: device buffers (3 * tile_w * tile_h / tile_w * tile_h floats), either may be
+ * NULL (both NULL: the count alone).  Ordered like rt_accum_resolve: on `stream`, after the accumulates issued so
+ * far, and the next accumulate waits for it; the call returns after synchronising on the result, with *above
+ * written.  Reads S and Q, never writes them.  RT_E_INVALID, and nothing changed (*above included): a plain
+ * accumulator, samples < 2, a floor or threshold that is not finite or not > 0, a stale scene binding.  Timed
+ * under RT_KF_COMPOSE when the accumulator's last rt_render_accumulate had RT_TIME_KERNELS. */
+int rt_accum_noise(rt_ctx* ctx, rt_accum* acc, double floor, double threshold, void* d_variance, void* d_error, uint64_t* above, void* stream);
+/* ... into host memory (plain path: device buffers for the call, copies out). */
+int rt_accum_noise_host(rt_ctx* ctx, rt_accum* acc, double floor, double threshold, float* variance, float* error, uint64_t* above);
+/* host only: the checkpoint of a moments accumulator.  The same 88-byte header with format version 2, followed by
+ * 3 * pixels f64 sums and then 3 * pixels f64 squares.  The version 2 reader refuses a version 1 file and
+ * rt_checkpoint_read refuses a version 2 file (RT_E_INVALID both ways); otherwise as rt_checkpoint_write / read,
+ * n_doubles / cap_doubles counting each of the two arrays (3 * tile_w * tile_h).  sums and squares both NULL:
+ * header only. */
+int rt_checkpoint_write_moments(const char* path, const rt_render_opts* opts, uint64_t scene_hash, uint32_t samples,
+                                const double* sums, const double* squares, size_t n_doubles);
+int rt_checkpoint_read_moments(const char* path, rt_render_opts* opts, uint64_t* scene_hash, uint32_t* samples, double* sums,
+                               double* squares, size_t cap_doubles);
 /* Diagnostic (device): the sphere test's division t = x / (2a) (shapes.rs:68,75)
  * computed as the device computes it (the per-ray reciprocal of 2a finished with
  * the division's own correction steps, DESIGN.md §4 "Division by 2a") -> fast[i],

@@ -229,6 +229,12 @@ struct FrameParams {
 };
 constexpr uint32_t kAaTallyGens = 1u;   // FrameParams::aa_flags: this pass's queue sizes go to gen_totals (the last
                                         //   pass of the last chunk; rays and shadow rays are tallied every pass)
+constexpr uint32_t kAaMoments = 2u;     // FrameParams::aa_flags: aa_acc is a moments accumulator's: the
+                                        //   squares' plane follows the tile's sums, so pixel p's three squares are at
+                                        //   aa_acc + 3 * tile_w * tile_h + 3p (aa_acc's per-chunk offset carries over).
+                                        //   Read by the launchers, which then take the kernels' kMom instantiations
+// Whether a launch takes the kernels' kMom instantiations (the sinks that also continue the squares).
+inline bool aa_moments(const FrameParams& fp) { return fp.aa_acc != nullptr && (fp.aa_flags & kAaMoments) != 0; }
 
 
 

@@ -207,5 +207,11 @@ hipError_t launch_path(const DevScene& sc, const FrameParams& fp, const PathStac
 // fp.aa_spp samples each: sum / samples, rounded once to f32 and quantised from the f64 value, written row by row
 // (fp.out_rgb / out_bgr, bgr_pitch, pad_end; rows [0, fp.rows)).  workgroups: the grid's upper bound.
 hipError_t launch_accum_resolve(const FrameParams& fp, uint32_t workgroups, hipStream_t s);
+// rt_accum_noise: the estimate of a moments accumulator (fp.aa_acc: the tile's sums, then the
+// plane of its sums of squares; fp.aa_spp >= 2 samples; rows [0, fp.rows) = the whole tile): variance (3 f32 per
+// pixel) and error (1 f32 per pixel), either may be null, and the pixels whose error is not <= threshold added to
+// *above, which the caller zeroed on s before.
+hipError_t launch_accum_noise(const FrameParams& fp, uint32_t workgroups, double err_floor, double threshold, float* variance,
+                              float* error, unsigned long long* above, hipStream_t s);
 
 }  // namespace rtamd

@@ -330,7 +330,10 @@ __device__ Col trace_path(const DevScene& sc, const BvhView& v, const FrameParam
 // the pixel's running sum in fp.aa_acc (3 f64 per tile pixel) with them, one sample at a time in
 // sample order: from 0.0 when fp.aa_pass is 0 (nothing read), else from the stored sum; the group's
 // lane 0 stores the sum.  No division, no write_pixel.
-template <int kNodes, bool kAccum = false>
+// kMoments (a moments accumulator; with kAccum only): the running sum of squares in
+// the plane after the tile's sums continues by the same rule, beside the sum: each lane squares its
+// own sample, the group adds the squares in sample order, lane 0 stores six doubles.
+template <int kNodes, bool kAccum = false, bool kMoments = false>
 __global__ __launch_bounds__(kPathBlock, RT_PATH_WAVES) void path_kernel(DevScene sc, FrameParams fp, PathStack st) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     double* s_srgb = reinterpret_cast<double*>(lds);
@@ -371,6 +374,12 @@ __global__ __launch_bounds__(kPathBlock, RT_PATH_WAVES) void path_kernel(DevScen
             sum = fp.aa_acc + 3 * (static_cast<size_t>(lr) * fp.tile_w + lx);
             if (first) res = Col{sum[0], sum[1], sum[2]};
         }
+        Col sq{0.0, 0.0, 0.0};
+        double* sqs = nullptr;
+        if constexpr (kMoments) {
+            sqs = sum + 3 * (static_cast<size_t>(fp.tile_w) * fp.tile_h);
+            if (first) sq = Col{sqs[0], sqs[1], sqs[2]};
+        }
         for (uint32_t a0 = 0; a0 < count; a0 += G) {
             const uint32_t a = first + a0 + gl;
             Col r{0.0, 0.0, 0.0};                                      // raytrace.rs:270-276
@@ -387,18 +396,26 @@ __global__ __launch_bounds__(kPathBlock, RT_PATH_WAVES) void path_kernel(DevScen
                 }
                 r = Col{r.r / ns, r.g / ns, r.b / ns};
             }
+            Col r2{0.0, 0.0, 0.0};                                     // the lane's own q = s * s (one rounding)
+            if constexpr (kMoments) r2 = Col{__dmul_rn(r.r, r.r), __dmul_rn(r.g, r.g), __dmul_rn(r.b, r.b)};
             if (G == 1) {
                 res = Col{res.r + r.r, res.g + r.g, res.b + r.b};
+                if constexpr (kMoments) sq = Col{__dadd_rn(sq.r, r2.r), __dadd_rn(sq.g, r2.g), __dadd_rn(sq.b, r2.b)};
             } else {
                 const uint32_t m = min(G, count - a0);
                 for (uint32_t j = 0; j < m; ++j) {                     // sample order
                     const int src = static_cast<int>(gbase + j);
                     res = Col{res.r + __shfl(r.r, src, 64), res.g + __shfl(r.g, src, 64), res.b + __shfl(r.b, src, 64)};
+                    if constexpr (kMoments)
+                        sq = Col{__dadd_rn(sq.r, __shfl(r2.r, src, 64)), __dadd_rn(sq.g, __shfl(r2.g, src, 64)),
+                                 __dadd_rn(sq.b, __shfl(r2.b, src, 64))};
                 }
             }
         }
         if constexpr (kAccum) {
             if (gl == 0) { sum[0] = res.r; sum[1] = res.g; sum[2] = res.b; }
+            if constexpr (kMoments)
+                if (gl == 0) { sqs[0] = sq.r; sqs[1] = sq.g; sqs[2] = sq.b; }
         } else {
             res = Col{res.r / aa, res.g / aa, res.b / aa};
             if (gl == 0) write_pixel(fp, lx, lr, res, s_srgb);
@@ -431,7 +448,10 @@ hipError_t launch_path(const DevScene& sc, const FrameParams& fp, const PathStac
     const uint64_t want = (npix * fp.path_group + kPathBlock - 1) / kPathBlock;   // path_group lanes per pixel
     const dim3 grid(static_cast<uint32_t>(want < st.T / kPathBlock ? want : st.T / kPathBlock));
     if (grid.x == 0) return hipSuccess;
-    if (accumulate) {                       // fp.aa_acc: the running sums; fp.aa_pass, fp.aa_spp: the samples
+    if (accumulate && (fp.aa_flags & kAaMoments)) {     // ... and the squares' plane after the tile's sums
+        if (staged) hipLaunchKernelGGL((path_kernel<2, true, true>), grid, dim3(kPathBlock), path_lds_bytes(sc, true), stream, sc, fp, st);
+        else hipLaunchKernelGGL((path_kernel<0, true, true>), grid, dim3(kPathBlock), path_lds_bytes(sc, false), stream, sc, fp, st);
+    } else if (accumulate) {                // fp.aa_acc: the running sums; fp.aa_pass, fp.aa_spp: the samples
         if (staged) hipLaunchKernelGGL((path_kernel<2, true>), grid, dim3(kPathBlock), path_lds_bytes(sc, true), stream, sc, fp, st);
         else hipLaunchKernelGGL((path_kernel<0, true>), grid, dim3(kPathBlock), path_lds_bytes(sc, false), stream, sc, fp, st);
     } else if (staged) hipLaunchKernelGGL(path_kernel<2>, grid, dim3(kPathBlock), path_lds_bytes(sc, true), stream, sc, fp, st);

@@ -11,6 +11,7 @@
 //            [--max-depth D] [--gpus N] [--band ROWS] [--jitter random|center] [--seed N]
 //            [--algo auto|wavefront|wavefront-aa|path|lds|global]
 //            [--progressive K] [--checkpoint FILE] [--aov PREFIX]
+//            [--until-noise T] [--noise-floor F] [--noise-pixels P] [--variance FILE.pfm]
 //            [--denoise ITER] [--denoise-flags normal,depth,color,demodulate|none]
 //
 // --denoise ITER: the image goes through the edge-avoiding a-trous filter (rt_denoise, ITER passes 1..8) before it is
@@ -28,8 +29,18 @@
 // so far and "samples done/total" goes to stderr.  --checkpoint FILE: FILE is written after every step
 // (the running sums, rt_checkpoint_write); a run that finds FILE continues from it when its options and
 // the scene's hash (FNV-1a 64 of the scene text) match, and refuses otherwise.  Both are single-device.
+// --progressive K --until-noise T [--noise-floor F] [--noise-pixels P]: the accumulator also keeps the sums of
+// squares (rt_accum_create_moments); after every step from 2 samples on, rt_accum_noise counts the pixels whose
+// relative error sqrt(variance of the mean) / (F + |mean|) is not <= T (F default 0.001), "noise above N" goes
+// to stderr, and the run stops when N <= P (default 0) or at --spp (a resumed run asks before its first step, and
+// then only writes the image of the samples it holds); the last line names the final sample count.
+// --variance FILE.pfm writes the variance image of the final samples (3 channels, rows as --aov's files).  With
+// either, --checkpoint writes format version 2 (sums and squares) and resumes only from a file of that kind, as a
+// run without them resumes only from version 1; a file of the other kind is left alone until the first step
+// overwrites it, and the run starts fresh with a message.
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -54,6 +65,11 @@ struct Args {
     unsigned long long seed = 1;       // keyed draws (the reference seeds from OS entropy, main.rs:43)
     long progressive = 0;              // samples per step (0: one render)
     std::string checkpoint;
+    double until_noise = 0;            // --until-noise T (0: run to --spp)
+    double noise_floor = 1e-3;
+    long noise_pixels = 0;
+    std::string variance;              // --variance FILE.pfm
+    bool moments() const { return until_noise != 0 || !variance.empty(); }
     std::string aov;                   // --aov PREFIX: write the feature buffers instead of the image
     long denoise = 0;                  // --denoise ITER: filter passes (0: off)
     unsigned denoise_flags = RT_DN_NORMAL | RT_DN_DEPTH;
@@ -92,6 +108,10 @@ bool parse_args(int argc, char** argv, Args& a) {
         else if (k == "--seed" && (v = val())) a.seed = std::strtoull(v, nullptr, 0);
         else if (k == "--progressive" && (v = val())) a.progressive = std::atol(v);
         else if (k == "--checkpoint" && (v = val())) a.checkpoint = v;
+        else if (k == "--until-noise" && (v = val())) a.until_noise = std::atof(v);
+        else if (k == "--noise-floor" && (v = val())) a.noise_floor = std::atof(v);
+        else if (k == "--noise-pixels" && (v = val())) a.noise_pixels = std::atol(v);
+        else if (k == "--variance" && (v = val())) a.variance = v;
         else if (k == "--aov" && (v = val())) a.aov = v;
         else if (k == "--denoise" && (v = val())) a.denoise = std::atol(v);
         else if (k == "--denoise-flags" && (v = val())) a.bad_denoise_flags = !parse_denoise_flags(v, a.denoise_flags);
@@ -106,6 +126,7 @@ bool parse_args(int argc, char** argv, Args& a) {
                                  "                [--max-depth D] [--gpus N] [--band ROWS] [--jitter random|center]\n"
                                  "                [--seed N] [--algo auto|wavefront|wavefront-aa|path|lds|global]\n"
                                  "                [--progressive K] [--checkpoint FILE] [--aov PREFIX]\n"
+                                 "                [--until-noise T] [--noise-floor F] [--noise-pixels P] [--variance FILE.pfm]\n"
                                  "                [--denoise ITER] [--denoise-flags normal,depth,color,demodulate|none]\n");
             return false;
         }
@@ -175,7 +196,10 @@ int run_denoised(const Args& a, rt_scene* scene, uint32_t W, uint32_t H, uint32_
     return done_with(0);
 }
 
-// --progressive / --checkpoint: one device, the whole frame in one accumulator, `total` samples in steps.
+bool write_pfm(const std::string& path, uint32_t W, uint32_t H, int channels, const float* data);
+
+// --progressive / --checkpoint / --until-noise / --variance: one device, the whole frame in one accumulator,
+// `total` samples in steps.
 int run_progressive(const Args& a, rt_scene* scene, const std::string& text, uint32_t W, uint32_t H, uint32_t total) {
     uint32_t pitch = 0;
     uint8_t hdr[122];
@@ -192,17 +216,32 @@ int run_progressive(const Args& a, rt_scene* scene, const std::string& text, uin
     rt_render_opts o;
     rt_render_opts_default(&o, W, H);
     o.max_depth = a.max_depth; o.jitter = a.jitter; o.seed = a.seed;
-    if (rt_accum_create(ctx, &o, &acc) != RT_OK) { std::printf("error: %s\n", rt_last_error(ctx)); return done_with(1); }
+    const bool moments = a.moments();
+    if ((moments ? rt_accum_create_moments(ctx, &o, &acc) : rt_accum_create(ctx, &o, &acc)) != RT_OK) {
+        std::printf("error: %s\n", rt_last_error(ctx));
+        return done_with(1);
+    }
     const uint64_t hash = fnv1a64(text);
     const size_t n_doubles = static_cast<size_t>(W) * H * 3;
-    std::vector<double> sums;
+    std::vector<double> sums, squares;
     uint32_t done = 0;
     if (!a.checkpoint.empty()) {
         sums.resize(n_doubles);
+        if (moments) squares.resize(n_doubles);
         rt_render_opts co;
         uint64_t ch = 0;
         uint32_t cs = 0;
-        const int rc = rt_checkpoint_read(a.checkpoint.c_str(), &co, &ch, &cs, nullptr, 0);
+        // the file of this run's kind: version 2 (sums and squares) with moments, version 1 without
+        auto read_ckpt = [&](bool m, double* s, double* q, size_t cap) {
+            return m ? rt_checkpoint_read_moments(a.checkpoint.c_str(), &co, &ch, &cs, s, q, cap)
+                     : rt_checkpoint_read(a.checkpoint.c_str(), &co, &ch, &cs, s, cap);
+        };
+        int rc = read_ckpt(moments, nullptr, nullptr, 0);
+        if (rc == RT_E_INVALID && read_ckpt(!moments, nullptr, nullptr, 0) == RT_OK) {
+            std::fprintf(stderr, "checkpoint %s holds %s: not resumed, starting fresh\n", a.checkpoint.c_str(),
+                         moments ? "sums without squares (format version 1)" : "sums and squares (format version 2)");
+            rc = RT_E_IO;
+        }
         if (rc == RT_OK) {
             const uint32_t cband = co.band ? co.band : 1, cstride = co.band_stride ? co.band_stride : 1;
             const bool same = co.width == W && co.height == H && co.x0 == 0 && co.tile_w == W && co.y0 == 0 && co.tile_h == H &&
@@ -213,8 +252,9 @@ int run_progressive(const Args& a, rt_scene* scene, const std::string& text, uin
                             !same ? "other options" : ch != hash ? "another scene" : "fewer samples than it holds");
                 return done_with(1);
             }
-            if (rt_checkpoint_read(a.checkpoint.c_str(), &co, &ch, &cs, sums.data(), sums.size()) != RT_OK ||
-                rt_accum_upload(ctx, acc, sums.data(), sums.size(), cs) != RT_OK) {
+            if (read_ckpt(moments, sums.data(), moments ? squares.data() : nullptr, sums.size()) != RT_OK ||
+                (moments ? rt_accum_upload_moments(ctx, acc, sums.data(), squares.data(), sums.size(), cs)
+                         : rt_accum_upload(ctx, acc, sums.data(), sums.size(), cs)) != RT_OK) {
                 std::printf("error: checkpoint %s: %s\n", a.checkpoint.c_str(), rt_last_error(nullptr));
                 return done_with(1);
             }
@@ -237,8 +277,22 @@ int run_progressive(const Args& a, rt_scene* scene, const std::string& text, uin
     uint64_t rays = 0;
     double kms = 0;
     auto t0 = std::chrono::steady_clock::now();
-    for (bool first = true; first || done < total; first = false) {
-        const uint32_t n = std::min(step, total - done);
+    // the stop rule: few enough pixels still above the threshold; 1 converged, 0 not, -1 an error
+    auto converged = [&]() {
+        uint64_t above = 0;
+        if (rt_accum_noise_host(ctx, acc, a.noise_floor, a.until_noise, nullptr, nullptr, &above) != RT_OK) return -1;
+        std::fprintf(stderr, "noise above %llu\n", static_cast<unsigned long long>(above));
+        return above <= static_cast<uint64_t>(std::max(0l, a.noise_pixels)) ? 1 : 0;
+    };
+    // a resumed render may have converged already: the rule is asked before any more samples are traced
+    bool stop = false;
+    if (a.until_noise != 0 && done >= 2 && done < total) {
+        const int cv = converged();
+        if (cv < 0) { std::printf("error: %s\n", rt_last_error(ctx)); return done_with(1); }
+        stop = cv == 1;
+    }
+    for (bool first = true; first || (done < total && !stop); first = false) {
+        const uint32_t n = stop ? 0u : std::min(step, total - done);
         rt_stats st{};
         if (n && (rt_render_accumulate(ctx, acc, n, a.algo, 0, nullptr) != RT_OK || rt_ctx_stats(ctx, &st) != RT_OK)) {
             std::printf("error: %s\n", rt_last_error(ctx));
@@ -261,12 +315,29 @@ int run_progressive(const Args& a, rt_scene* scene, const std::string& text, uin
         if (!a.checkpoint.empty() && n) {
             uint32_t cs = 0;
             if (rt_accum_download(ctx, acc, sums.data(), sums.size(), &cs) != RT_OK ||
-                rt_checkpoint_write(a.checkpoint.c_str(), &o, hash, cs, sums.data(), sums.size()) != RT_OK) {
+                (moments && rt_accum_download_moments(ctx, acc, squares.data(), squares.size()) != RT_OK) ||
+                (moments ? rt_checkpoint_write_moments(a.checkpoint.c_str(), &o, hash, cs, sums.data(), squares.data(), sums.size())
+                         : rt_checkpoint_write(a.checkpoint.c_str(), &o, hash, cs, sums.data(), sums.size())) != RT_OK) {
                 std::printf("error: checkpoint %s: %s\n", a.checkpoint.c_str(), rt_last_error(nullptr));
                 return done_with(1);
             }
         }
         std::fprintf(stderr, "samples %u/%u\n", done, total);
+        if (a.until_noise != 0 && done >= 2 && n) {
+            const int cv = converged();
+            if (cv < 0) { std::printf("error: %s\n", rt_last_error(ctx)); return done_with(1); }
+            if (cv == 1) break;
+        }
+    }
+    if (a.until_noise != 0) std::fprintf(stderr, "stopped at %u samples\n", done);
+    if (!a.variance.empty()) {
+        std::vector<float> var(n_doubles);
+        uint64_t above = 0;
+        if (rt_accum_noise_host(ctx, acc, a.noise_floor, a.until_noise != 0 ? a.until_noise : 1.0, var.data(), nullptr, &above) != RT_OK) {
+            std::printf("error: --variance: %s\n", rt_last_error(ctx));
+            return done_with(1);
+        }
+        if (!write_pfm(a.variance, W, H, 3, var.data())) { std::printf("error: cannot write %s\n", a.variance.c_str()); return done_with(1); }
     }
     const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     std::fprintf(stderr, "%ux%u spp=%u depth=%u gpus=1 progressive: %llu rays, kernels %.3f ms, wall %.3f s\n", W, H, done,
@@ -352,7 +423,7 @@ int main(int argc, char** argv) {
         }
         if (!a.aov.empty()) { std::printf("error: --denoise filters the image: not with --aov\n"); return 2; }
         if (spp == 0) { std::printf("error: --spp is 0 and the scene's antialias is 0\n"); return 1; }
-        if (a.progressive <= 0 && a.checkpoint.empty()) {
+        if (a.progressive <= 0 && a.checkpoint.empty() && !a.moments()) {
             const int rc = run_denoised(a, scene, W, H, spp);
             rt_scene_free(scene);
             return rc;
@@ -363,8 +434,9 @@ int main(int argc, char** argv) {
             std::printf("error: --aov renders on one device: not with --gpus %d\n", a.gpus);
             return 2;
         }
-        if (a.progressive > 0 || !a.checkpoint.empty()) {
-            std::printf("error: --aov writes the feature buffers of one render: not with --progressive or --checkpoint\n");
+        if (a.progressive > 0 || !a.checkpoint.empty() || a.moments()) {
+            std::printf("error: --aov writes the feature buffers of one render: not with --progressive, --checkpoint, "
+                        "--until-noise or --variance\n");
             return 2;
         }
         if (spp == 0) { std::printf("error: --spp is 0 and the scene's antialias is 0\n"); return 1; }
@@ -372,11 +444,22 @@ int main(int argc, char** argv) {
         rt_scene_free(scene);
         return rc;
     }
-    if (a.progressive > 0 || !a.checkpoint.empty()) {
-        if (a.gpus > 1) {
-            std::printf("error: --progressive and --checkpoint render on one device: not with --gpus %d\n", a.gpus);
+    if (a.moments()) {
+        if (a.until_noise != 0 && (!(a.until_noise > 0) || !std::isfinite(a.until_noise) || a.progressive <= 0)) {
+            std::printf("error: --until-noise takes a finite threshold > 0 and needs --progressive K (the stop rule is asked after every step)\n");
             return 2;
         }
+        if (!(a.noise_floor > 0) || !std::isfinite(a.noise_floor) || a.noise_pixels < 0) {
+            std::printf("error: --noise-floor takes a finite value > 0, --noise-pixels a count >= 0\n");
+            return 2;
+        }
+    }
+    if (a.progressive > 0 || !a.checkpoint.empty() || a.moments()) {
+        if (a.gpus > 1) {
+            std::printf("error: --progressive, --checkpoint, --until-noise and --variance render on one device: not with --gpus %d\n", a.gpus);
+            return 2;
+        }
+        if (a.moments() && spp < 2) { std::printf("error: --until-noise and --variance need --spp of at least 2 (a variance of 2 samples)\n"); return 2; }
         if (spp == 0) { std::printf("error: --spp is 0 and the scene's antialias is 0\n"); return 1; }
         const int rc = run_progressive(a, scene, text, W, H, spp);
         rt_scene_free(scene);

@@ -91,6 +91,42 @@ uint32_t plan_path_group(uint64_t npix, uint32_t samples, uint32_t T_full, int64
     return G;
 }
 
+bool plan_accum_doubles(uint64_t pixels, bool moments, uint64_t* doubles) {
+    const uint64_t per = moments ? 6 : 3;
+    if (pixels > UINT64_MAX / (8 * per)) return false;
+    *doubles = per * pixels;
+    return true;
+}
+
+int plan_accum_call(AccumCall call, bool has_moments, const char** err) {
+    if (call == AccumCall::upload) {
+        if (!has_moments) return RT_OK;
+        *err = "rt_accum_upload on a moments accumulator would leave its squares stale: rt_accum_upload_moments";
+        return RT_E_INVALID;
+    }
+    if (has_moments) return RT_OK;
+    *err = call == AccumCall::noise ? "the accumulator keeps no second moments (rt_accum_create_moments)"
+                                    : "a plain accumulator has no squares to move (rt_accum_create_moments)";
+    return RT_E_INVALID;
+}
+
+int plan_noise(bool has_moments, uint32_t samples, double floor, double threshold, const char** err) {
+    if (const int rc = plan_accum_call(AccumCall::noise, has_moments, err); rc != RT_OK) return rc;
+    if (samples < 2) {
+        *err = "a variance needs at least 2 samples";
+        return RT_E_INVALID;
+    }
+    if (!std::isfinite(floor) || !(floor > 0.0)) {
+        *err = "the noise floor must be finite and > 0";
+        return RT_E_INVALID;
+    }
+    if (!std::isfinite(threshold) || !(threshold > 0.0)) {
+        *err = "the noise threshold must be finite and > 0";
+        return RT_E_INVALID;
+    }
+    return RT_OK;
+}
+
 SourcePair plan_sources(const SceneFacts& sf, const int64_t* tune, int mode) {
     SourcePair p;
     if (mode != RT_ALGO_WAVEFRONT) {

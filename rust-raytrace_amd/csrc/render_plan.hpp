@@ -69,6 +69,19 @@ int plan_accumulate(const SceneFacts& sf, int algo, uint32_t flags, uint32_t fir
 // the `samples` this launch traces per pixel; a power of two <= 64.  override_g: tuning path_group (0: none).
 uint32_t plan_path_group(uint64_t npix, uint32_t samples, uint32_t T_full, int64_t override_g);
 
+// ---- moments accumulators (rt_accum_create_moments) ------------------------
+// The accumulator's device buffer in doubles: 3 per tile pixel, the sums; with moments 3 more per pixel, the sums
+// of squares, as a plane of their own after the sums (24 B / 48 B per pixel).  false: the bytes pass 2^64.
+bool plan_accum_doubles(uint64_t pixels, bool moments, uint64_t* doubles);
+// Which kind of accumulator a call takes.  rt_accum_upload replaces the sums alone, which would leave a moments
+// accumulator's squares stale: refused there; rt_accum_upload_moments / download_moments and the noise calls need
+// the squares: refused on a plain accumulator.  Every other call works on both kinds.
+enum class AccumCall { upload, upload_moments, download_moments, noise };
+int plan_accum_call(AccumCall call, bool has_moments, const char** err);
+// rt_accum_noise / rt_accum_noise_host: a moments accumulator of at least 2 samples (the variance divides by
+// N - 1), and a floor and a threshold that are finite and > 0.  RT_OK, or RT_E_INVALID with its text in *err.
+int plan_noise(bool has_moments, uint32_t samples, double floor, double threshold, const char** err);
+
 // ---- sphere sources ---------------------------------------------------------------------
 // (nearest, occlusion) sphere sources of a wavefront render, see launch_api.hpp; pfx2 / pfxq: the
 // nodes of the binary / quantised tree a prefix source stages in LDS (DevScene::pfx2 / pfxq, which

@@ -6,6 +6,7 @@
 #include <algorithm>
 #include <cstdio>
 
+#include "host_staging.hpp"
 #include "rt_ctx.hpp"
 
 using namespace rtamd;
@@ -59,7 +60,7 @@ int check_pitch(rt_ctx* c, const rt_accum* a, uint32_t bgr_pitch, uint32_t& pitc
     return RT_OK;
 }
 
-int accum_create(rt_ctx* c, const rt_render_opts* o, rt_accum** out) {
+int accum_create(rt_ctx* c, const rt_render_opts* o, bool moments, rt_accum** out) {
     if (!c->has_scene) return fail(c, RT_E_NOSCENE, "no scene uploaded");
     // the options' own checks, as a render makes them (render_accumulate with no samples renders nothing)
     rt_render_opts b = *o;
@@ -74,9 +75,21 @@ int accum_create(rt_ctx* c, const rt_render_opts* o, rt_accum** out) {
     a->o = b;
     a->scene_gen = c->scene_gen;
     a->npix = static_cast<uint64_t>(o->tile_w) * o->tile_h;
+    a->moments = moments;
+    // the sums and, with moments, the plane of the sums of squares after them: one allocation, made here, so
+    // that a reserved accumulate allocates nothing
+    uint64_t doubles = 0;
+    if (!plan_accum_doubles(a->npix, moments, &doubles)) {      // (two 32-bit sides can pass 2^64 / 48)
+        delete a;
+        return fail(c, RT_E_NOMEM, "the accumulator's sums do not fit");
+    }
     hipError_t e = hipEventCreateWithFlags(&a->read_done, hipEventDisableTiming);
-    if (e == hipSuccess && a->npix) e = hipMalloc(reinterpret_cast<void**>(&a->d_sums), a->npix * 3 * sizeof(double));
+    if (e == hipSuccess && a->npix) e = hipMalloc(reinterpret_cast<void**>(&a->d_sums), doubles * sizeof(double));
+    if (e == hipSuccess && moments) e = hipMalloc(reinterpret_cast<void**>(&a->d_above), sizeof(unsigned long long));
+    if (e == hipSuccess && moments) e = hipHostMalloc(reinterpret_cast<void**>(&a->h_above), sizeof(unsigned long long), hipHostMallocDefault);
     if (e != hipSuccess) {
+        if (a->d_sums) (void)hipFree(a->d_sums);
+        if (a->d_above) (void)hipFree(a->d_above);
         if (a->read_done) (void)hipEventDestroy(a->read_done);
         delete a;
         (void)hipGetLastError();
@@ -99,7 +112,7 @@ int accumulate(rt_ctx* c, rt_accum* a, uint32_t n, int32_t algo, uint32_t flags,
         HIP_TRY(c, hipStreamWaitEvent(st, a->read_done, 0));
         a->read_pending = false;
     }
-    if (const int rc = render_accumulate(c, &o, a->d_sums, a->samples, n, stream); rc != RT_OK) return rc;
+    if (const int rc = render_accumulate(c, &o, a->d_sums, a->samples, n, stream, a->moments); rc != RT_OK) return rc;
     if (n) {
         a->samples += n;
         a->timed = (flags & RT_TIME_KERNELS) != 0;
@@ -160,6 +173,8 @@ int download(rt_ctx* c, rt_accum* a, double* sums, size_t cap, uint32_t* samples
 
 int upload(rt_ctx* c, rt_accum* a, const double* sums, size_t n, uint32_t samples) {
     if (const int rc = usable(c, a, "rt_accum_upload"); rc != RT_OK) return rc;
+    const char* refusal = nullptr;
+    if (const int rc = plan_accum_call(AccumCall::upload, a->moments, &refusal); rc != RT_OK) return fail(c, rc, refusal);
     if (n != 3 * a->npix || (!sums && n)) return fail(c, RT_E_INVALID, "rt_accum_upload: not 3 * tile_w * tile_h doubles");
     if (samples > kAccumMaxSamples) return fail(c, RT_E_INVALID, "rt_accum_upload: samples above 2^31");
     HIP_TRY(c, hipSetDevice(c->device));
@@ -171,6 +186,101 @@ int upload(rt_ctx* c, rt_accum* a, const double* sums, size_t n, uint32_t sample
     return RT_OK;
 }
 
+// rt_accum_download_moments: the squares' plane (of no samples: zeros, as the sums').
+int download_moments(rt_ctx* c, rt_accum* a, double* squares, size_t cap) {
+    if (const int rc = usable(c, a, "rt_accum_download_moments"); rc != RT_OK) return rc;
+    const char* refusal = nullptr;
+    if (const int rc = plan_accum_call(AccumCall::download_moments, a->moments, &refusal); rc != RT_OK) return fail(c, rc, refusal);
+    if (cap < 3 * a->npix || (!squares && a->npix))
+        return fail(c, RT_E_INVALID, "rt_accum_download_moments: fewer than 3 * tile_w * tile_h doubles");
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (const int rc = order_on(c, a, c->stream, false); rc != RT_OK) return rc;
+    if (a->npix && a->samples)
+        HIP_TRY(c, hipMemcpyAsync(squares, a->d_sums + 3 * a->npix, a->npix * 3 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (a->samples == 0) std::fill(squares, squares + 3 * a->npix, 0.0);
+    return check_join_error(c);
+}
+
+// rt_accum_upload_moments: sums, squares and count together, so neither plane is ever stale.
+int upload_moments(rt_ctx* c, rt_accum* a, const double* sums, const double* squares, size_t n, uint32_t samples) {
+    if (const int rc = usable(c, a, "rt_accum_upload_moments"); rc != RT_OK) return rc;
+    const char* refusal = nullptr;
+    if (const int rc = plan_accum_call(AccumCall::upload_moments, a->moments, &refusal); rc != RT_OK) return fail(c, rc, refusal);
+    if (n != 3 * a->npix || ((!sums || !squares) && n))
+        return fail(c, RT_E_INVALID, "rt_accum_upload_moments: not 3 * tile_w * tile_h doubles of each");
+    if (samples > kAccumMaxSamples) return fail(c, RT_E_INVALID, "rt_accum_upload_moments: samples above 2^31");
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (const int rc = order_on(c, a, c->stream, true); rc != RT_OK) return rc;
+    if (n) {
+        HIP_TRY(c, hipMemcpyAsync(a->d_sums, sums, n * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(a->d_sums + n, squares, n * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    }
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    a->samples = samples;
+    return RT_OK;
+}
+
+// The checks of both noise calls; nothing has changed when one refuses.
+int check_noise(rt_ctx* c, rt_accum* a, double floor, double threshold, const char* what) {
+    if (const int rc = usable(c, a, what); rc != RT_OK) return rc;
+    const char* refusal = nullptr;
+    if (const int rc = plan_noise(a->moments, a->samples, floor, threshold, &refusal); rc != RT_OK)
+        return fail(c, rc, std::string(what) + ": " + refusal);
+    return RT_OK;
+}
+
+// accum_noise over the whole tile on st, ordered as a resolve is (a reader of the sums); the count comes back
+// once st has run it.
+int noise_device(rt_ctx* c, rt_accum* a, double floor, double threshold, float* d_var, float* d_err, uint64_t* above, hipStream_t st) {
+    if (a->npix == 0) {
+        *above = 0;
+        return RT_OK;
+    }
+    if (const int rc = order_on(c, a, st, false); rc != RT_OK) return rc;
+    HIP_TRY(c, hipMemsetAsync(a->d_above, 0, sizeof(unsigned long long), st));
+    FrameParams fp{};
+    fp.tile_w = a->o.tile_w; fp.tile_h = a->o.tile_h;
+    fp.row0 = 0; fp.rows = a->o.tile_h;
+    fp.aa_acc = a->d_sums;
+    fp.aa_spp = a->samples;
+    LaunchMarks m;
+    m.pool = &c->tev; m.used = &c->t_used; m.out = &c->tint;
+    if (a->timed) HIP_TRY(c, m.begin(st));
+    HIP_TRY(c, launch_accum_noise(fp, 4u * static_cast<uint32_t>(c->n_cu), floor, threshold, d_var, d_err, a->d_above, st));
+    if (a->timed) HIP_TRY(c, m.mark(st, kKfCompose));
+    // the count lands in the accumulator's own page-locked word: nothing queued points into this frame
+    HIP_TRY(c, hipMemcpyAsync(a->h_above, a->d_above, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipEventRecord(a->read_done, st));
+    a->read_pending = true;
+    HIP_TRY(c, hipStreamSynchronize(st));
+    *above = *a->h_above;
+    return RT_OK;
+}
+
+int noise(rt_ctx* c, rt_accum* a, double floor, double threshold, void* d_var, void* d_err, uint64_t* above, void* stream) {
+    if (const int rc = check_noise(c, a, floor, threshold, "rt_accum_noise"); rc != RT_OK) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const hipStream_t st = stream ? static_cast<hipStream_t>(stream) : c->stream;
+    return noise_device(c, a, floor, threshold, static_cast<float*>(d_var), static_cast<float*>(d_err), above, st);
+}
+
+int noise_host(rt_ctx* c, rt_accum* a, double floor, double threshold, float* variance, float* error, uint64_t* above) {
+    if (const int rc = check_noise(c, a, floor, threshold, "rt_accum_noise_host"); rc != RT_OK) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t bytes[2] = {variance ? a->npix * 3 * sizeof(float) : 0, error ? a->npix * sizeof(float) : 0};
+    const void* const in[2] = {nullptr, nullptr};
+    void* const out[2] = {variance, error};
+    uint64_t n = 0;
+    const StagedTexts texts{"rt_accum_noise_host", "rt_accum_noise_host: copy", "rt_accum_noise_host: synchronise"};
+    const int rc = run_staged<2>(c, bytes, in, out, texts, [&](const Staged<2>& s) {
+        return noise_device(c, a, floor, threshold, s.as<float>(0), s.as<float>(1), &n, c->stream);
+    });
+    if (rc != RT_OK) return rc;
+    *above = n;
+    return check_join_error(c);
+}
+
 // The accumulator's device resources, once nothing on the device uses them.
 void release(rt_accum* a) {
     rt_ctx* c = a->ctx;
@@ -178,8 +288,12 @@ void release(rt_accum* a) {
     if (c->render_pending) (void)hipEventSynchronize(c->render_done);
     if (a->read_pending) (void)hipEventSynchronize(a->read_done);
     if (a->d_sums) (void)hipFree(a->d_sums);
+    if (a->d_above) (void)hipFree(a->d_above);
+    if (a->h_above) (void)hipHostFree(a->h_above);
     if (a->read_done) (void)hipEventDestroy(a->read_done);
     a->d_sums = nullptr;
+    a->d_above = nullptr;
+    a->h_above = nullptr;
     a->read_done = nullptr;
     a->read_pending = false;
     a->ctx = nullptr;
@@ -201,7 +315,19 @@ extern "C" {
 int rt_accum_create(rt_ctx* c, const rt_render_opts* o, rt_accum** out) {
     if (!c || !o || !out) return RT_E_INVALID;
     *out = nullptr;
-    return guarded(c, [&] { return accum_create(c, o, out); });
+    return guarded(c, [&] { return accum_create(c, o, false, out); });
+}
+
+int rt_accum_create_moments(rt_ctx* c, const rt_render_opts* o, rt_accum** out) {
+    if (!c || !o || !out) return RT_E_INVALID;
+    *out = nullptr;
+    return guarded(c, [&] { return accum_create(c, o, true, out); });
+}
+
+int rt_accum_has_moments(const rt_accum* a, int32_t* flag) {
+    if (!a || !flag) return RT_E_INVALID;
+    *flag = a->moments ? 1 : 0;
+    return RT_OK;
 }
 
 void rt_accum_destroy(rt_accum* a) {
@@ -251,6 +377,27 @@ int rt_accum_download(rt_ctx* c, rt_accum* a, double* sums, size_t cap_doubles, 
 int rt_accum_upload(rt_ctx* c, rt_accum* a, const double* sums, size_t n_doubles, uint32_t samples) {
     if (!c || !a) return RT_E_INVALID;
     return guarded(c, [&] { return upload(c, a, sums, n_doubles, samples); });
+}
+
+int rt_accum_download_moments(rt_ctx* c, rt_accum* a, double* squares, size_t cap_doubles) {
+    if (!c || !a) return RT_E_INVALID;
+    return guarded(c, [&] { return download_moments(c, a, squares, cap_doubles); });
+}
+
+int rt_accum_upload_moments(rt_ctx* c, rt_accum* a, const double* sums, const double* squares, size_t n_doubles, uint32_t samples) {
+    if (!c || !a) return RT_E_INVALID;
+    return guarded(c, [&] { return upload_moments(c, a, sums, squares, n_doubles, samples); });
+}
+
+int rt_accum_noise(rt_ctx* c, rt_accum* a, double floor, double threshold, void* d_variance, void* d_error, uint64_t* above,
+                   void* stream) {
+    if (!c || !a || !above) return RT_E_INVALID;
+    return guarded(c, [&] { return noise(c, a, floor, threshold, d_variance, d_error, above, stream); });
+}
+
+int rt_accum_noise_host(rt_ctx* c, rt_accum* a, double floor, double threshold, float* variance, float* error, uint64_t* above) {
+    if (!c || !a || !above) return RT_E_INVALID;
+    return guarded(c, [&] { return noise_host(c, a, floor, threshold, variance, error, above); });
 }
 
 }  // extern "C"

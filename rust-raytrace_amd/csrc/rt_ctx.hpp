@@ -54,6 +54,7 @@ struct RenderReq {
     bool accumulate = false;
     double* acc = nullptr;             // (null: an empty tile)
     uint32_t acc_first = 0, acc_n = 0;
+    bool acc_moments = false;          // a moments accumulator: the squares' plane follows the tile's sums (kAaMoments)
 };
 
 }  // namespace rtamd
@@ -68,6 +69,10 @@ struct rt_accum {
     double* d_sums = nullptr;          // 3 * npix f64, tile row-major (null: an empty tile)
     uint64_t npix = 0;
     uint32_t samples = 0;
+    bool moments = false;              // rt_accum_create_moments: d_sums holds 6 * npix doubles, the sums and then the
+                                       //   plane of the sums of squares
+    unsigned long long* d_above = nullptr;   // rt_accum_noise's counter (allocated with a moments accumulator)
+    unsigned long long* h_above = nullptr;   // ... and where its value lands on the host (page-locked, the accumulator's)
     bool timed = false;                // the last accumulate had RT_TIME_KERNELS: a resolve is timed too
     // a device resolve reads the sums on a caller's stream: the next accumulate (which writes them) waits for it
     hipEvent_t read_done = nullptr;
@@ -256,7 +261,9 @@ void drop_lanes(rt_ctx* c);
 int check_join_error(rt_ctx* c);
 // rt_render_accumulate behind its argument checks: one render of o's tile (o: the accumulator's bound options
 // with the call's algo and flags) that adds samples [first, first + n) to `sums`.  n == 0: the checks only.
-int render_accumulate(rt_ctx* c, const rt_render_opts* o, double* sums, uint32_t first, uint32_t n, void* stream);
+// moments: `sums` is a moments accumulator's (6 f64 per tile pixel: the sums, then the plane of the sums of squares).
+int render_accumulate(rt_ctx* c, const rt_render_opts* o, double* sums, uint32_t first, uint32_t n, void* stream,
+                      bool moments = false);
 
 // rt_render_aov behind its argument checks: one render of o's tile into the selected device buffers of `out`
 // (channels: the rt_aov mask, for the verbose line) on `stream` (null: the context's own).

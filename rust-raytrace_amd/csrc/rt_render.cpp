@@ -433,7 +433,7 @@ int launch_chunks(rt_ctx* c, const rt_render_opts* o, RenderReq req, const Rende
             const bool last = a + 1 == passes;
             f.aa_pass = req.acc_first + a;
             f.aa_acc = req.accumulate ? req.acc + 3 * static_cast<size_t>(f.row0) * f.tile_w : p.aa ? L.acc : nullptr;
-            f.aa_flags = p.aa && last && ci + 1 == p.cp.n_chunks ? kAaTallyGens : 0u;
+            f.aa_flags = (p.aa && last && ci + 1 == p.cp.n_chunks ? kAaTallyGens : 0u) | (req.acc_moments ? kAaMoments : 0u);
             WfStreams wp = ws;
             if (!last) wp.fold_ev = nullptr;
             HIP_TRY(c, launch_wavefront(c->dsc, f, b, p.sp.src, p.sp.src_occ, run.count, wp, last ? L.mark : nullptr,
@@ -513,9 +513,9 @@ int render_wavefront(rt_ctx* c, const rt_render_opts* o, RenderReq req, const Re
         std::fprintf(stderr, "rtamd: aa passes %u, chunks %u x %u rows, resolve after each chunk's last pass, sums %s\n",
                      fp.aa_spp, p.cp.n_chunks, p.cp.chunk_rows, c->t(kTuneCompose) ? "row by row (compose)" : "per pixel");
     if (req.accumulate && c->t(kTuneVerbose))
-        std::fprintf(stderr, "rtamd: accumulate samples [%u, %u) passes\n"
+        std::fprintf(stderr, "rtamd: accumulate samples [%u, %u) passes%s\n"
                              "rtamd: aa passes %u, chunks %u x %u rows, no resolve (the accumulator keeps the sums), sums %s\n",
-                     req.acc_first, req.acc_first + req.acc_n, req.acc_n, p.cp.n_chunks, p.cp.chunk_rows,
+                     req.acc_first, req.acc_first + req.acc_n, req.acc_moments ? " moments" : "", req.acc_n, p.cp.n_chunks, p.cp.chunk_rows,
                      c->t(kTuneCompose) ? "row by row (compose)" : "per pixel");
     return launch_chunks(c, o, req, rcall, p);
 }
@@ -535,6 +535,7 @@ int render_path(rt_ctx* c, const rt_render_opts* o, RenderReq req, RenderCall& r
         rcall.fp.aa_pass = req.acc_first;
         rcall.fp.aa_spp = req.acc_n;
         rcall.fp.aa_acc = req.acc;
+        rcall.fp.aa_flags = req.acc_moments ? kAaMoments : 0u;
     }
     const uint32_t T = static_cast<uint32_t>(std::min<uint64_t>(T_full, (npix * G + 255) / 256 * 256));
     PathStack ps{};
@@ -554,7 +555,8 @@ int render_path(rt_ctx* c, const rt_render_opts* o, RenderReq req, RenderCall& r
     if (const int rc = zero_counters(c, st); rc != RT_OK) return rc;
     const bool staged = path_lds_bytes(c->dsc, true) <= 48 * 1024;
     if (req.accumulate && c->t(kTuneVerbose))
-        std::fprintf(stderr, "rtamd: accumulate samples [%u, %u) path\n", req.acc_first, req.acc_first + req.acc_n);
+        std::fprintf(stderr, "rtamd: accumulate samples [%u, %u) path%s\n", req.acc_first, req.acc_first + req.acc_n,
+                     req.acc_moments ? " moments" : "");
     if (c->t(kTuneVerbose))
         std::fprintf(stderr, "rtamd: path G %u T %u staged %d npix %llu\n", G, T, staged ? 1 : 0,
                      static_cast<unsigned long long>(npix));
@@ -739,12 +741,13 @@ int warm_streams(rt_ctx* c, const std::vector<hipStream_t>& ss) {
     return RT_OK;
 }
 
-int render_accumulate(rt_ctx* c, const rt_render_opts* o, double* sums, uint32_t first, uint32_t n, void* stream) {
+int render_accumulate(rt_ctx* c, const rt_render_opts* o, double* sums, uint32_t first, uint32_t n, void* stream, bool moments) {
     RenderReq req;
     req.accumulate = true;
     req.acc = sums;
     req.acc_first = first;
     req.acc_n = n;
+    req.acc_moments = moments;
     return render_device(c, o, nullptr, nullptr, stream, req);
 }
 

@@ -507,23 +507,35 @@ __device__ __forceinline__ Col aa_sample(Col c) { return Col{(0.0 + c.r) / 1.0, 
 // pixel p: pass 0 starts from BLACK (0.0 + s_0, nothing read), pass a adds s_a to
 // the sum of samples 0 .. a-1.  A pixel has one writer per pass and the passes
 // of a chunk follow each other on its lane's stream: plain loads and stores.
+// kMom (a moments accumulator; instantiations of their own, so a plain accumulator and a
+// one-shot antialiased render run the kernels they always ran): the running sums of squares in the plane after
+// the tile's sums continue by the same rule, pass 0 stores 0.0 + s * s.
+// One sample's step of a running sum of squares: q = s * s, then Q + q, two IEEE operations and never an fma.
+__device__ __forceinline__ double sq_add(double Q, double s) { return __dadd_rn(Q, __dmul_rn(s, s)); }
+template <bool kMom = false>
 __device__ __forceinline__ void aa_add(const FrameParams& fp, uint32_t p, Col s) {
     double* q = fp.aa_acc + 3 * static_cast<size_t>(p);
     Col acc{0.0, 0.0, 0.0};
     if (fp.aa_pass) acc = Col{q[0], q[1], q[2]};
     q[0] = acc.r + s.r; q[1] = acc.g + s.g; q[2] = acc.b + s.b;
+    if constexpr (kMom) {
+        double* q2 = q + 3 * (static_cast<size_t>(fp.tile_w) * fp.tile_h);
+        Col sq{0.0, 0.0, 0.0};
+        if (fp.aa_pass) sq = Col{q2[0], q2[1], q2[2]};
+        q2[0] = sq_add(sq.r, s.r); q2[1] = sq_add(sq.g, s.g); q2[2] = sq_add(sq.b, s.b);
+    }
 }
 
 // The final colour of chain c (pixel p of the chunk): into ccol[c] for wf_compose
 // (chain order: coalesced), or straight into the frame.  kAa (res: the sample's
 // colour): into term[c] (the chain's terminal, folded by now) for wf_aa_compose,
 // or added to pixel p's running sum.
-template <bool kAa = false>
+template <bool kAa = false, bool kMom = false>
 __device__ __forceinline__ void emit_chain(const FrameParams& fp, const WfBufs& b, uint32_t c, uint32_t p, Col res,
                                            const double* srgb) {
     if constexpr (kAa) {
         if (b.compose) { stn(&b.term(0)[c], res.r); stn(&b.term(1)[c], res.g); stn(&b.term(2)[c], res.b); }
-        else aa_add(fp, p, res);
+        else aa_add<kMom>(fp, p, res);
     } else if (b.compose) {
         const uint32_t q = pack_bgr(res, srgb);
         const U32x4 v = {__float_as_uint(static_cast<float>(res.r)), __float_as_uint(static_cast<float>(res.g)),

@@ -29,7 +29,7 @@ namespace {
 // RT_FOLD_THREADS-thread workgroups (256: at the fold's ~96 VGPRs five of them,
 // 20 waves, fit a CU where one 1024-thread workgroup leaves 4 wave slots idle),
 // dealt block-major over (kWfThreads / RT_FOLD_THREADS) x G workgroups.
-template <bool kFresnel, bool kAa = false, bool kPack = false>
+template <bool kFresnel, bool kAa = false, bool kPack = false, bool kMom = false>
 __global__ __launch_bounds__(RT_FOLD_THREADS, RT_FOLD_WAVES) void wf_fold(DevScene sc, FrameParams fp, WfBufs b, uint32_t lo,
                                                                           uint32_t hi) {
     constexpr int kT = RT_FOLD_THREADS;
@@ -64,7 +64,7 @@ __global__ __launch_bounds__(RT_FOLD_THREADS, RT_FOLD_WAVES) void wf_fold(DevSce
         if (cur.nlev >= lo && cur.nlev <= hi) {             // (kNlevRunning: not ended yet, or no chain)
             const Col folded = fold_levels<kFresnel, kPack>(sc, b, cur.c, static_cast<int>(cur.nlev), cur.term);
             const Col res = kAa ? aa_sample(folded) : average_samples(folded, fp.spp);
-            emit_chain<kAa>(fp, b, cur.c, cur.p, res, s_srgb);
+            emit_chain<kAa, kMom>(fp, b, cur.c, cur.p, res, s_srgb);
         }
         cur = nxt;
     }
@@ -109,11 +109,15 @@ hipError_t launch_fold(const DevScene& sc, const FrameParams& fp, const WfBufs& 
     if (m && (e = m->begin(s)) != hipSuccess) return e;
     // kAa (RT_ALGO_WAVEFRONT_AA): the sample's colour to the running sums
     (void)dispatch_bools(
-        [&](auto kFresnel, auto kAa, auto kPack) {
-            hipLaunchKernelGGL((wf_fold<kFresnel(), kAa(), kPack()>), grid, block, 0, s, sc, fp, b, lo, hi);
-            return hipSuccess;
+        [&](auto kFresnel, auto kAa, auto kPack, auto kMom) {
+            if constexpr (kMom() && !kAa()) {                  // (kMom: a moments accumulator's passes only)
+                return hipErrorInvalidValue;
+            } else {
+                hipLaunchKernelGGL((wf_fold<kFresnel(), kAa(), kPack(), kMom()>), grid, block, 0, s, sc, fp, b, lo, hi);
+                return hipSuccess;
+            }
         },
-        sc.has_fresnel, fp.aa_acc != nullptr, packed);
+        sc.has_fresnel, fp.aa_acc != nullptr, packed, aa_moments(fp));
     return m ? m->mark(s, kKfFold) : hipGetLastError();
 }
 

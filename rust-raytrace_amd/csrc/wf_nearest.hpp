@@ -66,7 +66,8 @@ namespace {
 // generation's leaves the ray's direction as the chain's terminal (set_sky_terminal); a camera
 // ray's is noted in pmap (compose, as ever) or csky, and wf_compose / wf_aa_compose / wf_sky_pixels
 // rebuild the ray and write the pixel or add its sample.
-template <bool kCam, bool kFresnel, bool kAa = false, bool kSky = false>
+// kMom (kAa only): ... and its square to the running sum of squares (aa_add<true>).
+template <bool kCam, bool kFresnel, bool kAa = false, bool kSky = false, bool kMom = false>
 __device__ __forceinline__ void finish_nearest(const DevScene& sc, const FrameParams& fp, const WfBufs& b,
                                                const DevSphere* sph, int k, bool live, const Ray& r, double sig,
                                                uint32_t p, const Hit& h, uint32_t* counts, size_t obase, size_t rbase) {
@@ -82,7 +83,7 @@ __device__ __forceinline__ void finish_nearest(const DevScene& sc, const FramePa
             if constexpr (kCam) {                                           // no levels: final now
                 if (b.compose) stn(&b.pmap()[p], kPixBackground);
                 else if constexpr (kSky) { /* csky below: wf_sky_pixels */ }
-                else if constexpr (kAa) aa_add(fp, p, Col{fp.aa_bg[0], fp.aa_bg[1], fp.aa_bg[2]});
+                else if constexpr (kAa) aa_add<kMom>(fp, p, Col{fp.aa_bg[0], fp.aa_bg[1], fp.aa_bg[2]});
                 else write_background_pixel(fp, b, p);
             } else if constexpr (kSky) {
                 set_sky_terminal(b, p, r, k);
@@ -118,7 +119,7 @@ __device__ __forceinline__ void finish_nearest(const DevScene& sc, const FramePa
     if (ends) {
         if constexpr (kCam) {                              // no levels: the final pixel now
             if (b.compose) stn(&b.pmap()[p], kPixAmbient | static_cast<uint32_t>(end_obj));
-            else if constexpr (kAa) aa_add(fp, p, aa_sample(end_colour(sc, end_obj)));
+            else if constexpr (kAa) aa_add<kMom>(fp, p, aa_sample(end_colour(sc, end_obj)));
             else write_pixel(fp, p % fp.tile_w, fp.row0 + p / fp.tile_w, average_samples(end_colour(sc, end_obj), fp.spp));
         } else {
             set_terminal(b, p, end_colour(sc, end_obj), k);
@@ -166,7 +167,7 @@ __device__ __forceinline__ void finish_nearest(const DevScene& sc, const FramePa
 // its reflection ray (raytrace.rs:58-64) to Q_{k+1} right here: the next
 // generation depends only on the hit, never on the shadow rays or the Phong
 // sum, so those run on the other stream, off the critical path.
-template <int kSrc, bool kCam, bool kCount, bool kFresnel, bool kAa = false, bool kSky = false>
+template <int kSrc, bool kCam, bool kCount, bool kFresnel, bool kAa = false, bool kSky = false, bool kMom = false>
 __global__ __launch_bounds__(kWfThreads, Src<kSrc>::waves) void wf_nearest(DevScene sc, FrameParams fp, WfBufs b, int k) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
 #ifndef RT_NEAR_PRIO
@@ -228,7 +229,7 @@ __global__ __launch_bounds__(kWfThreads, Src<kSrc>::waves) void wf_nearest(DevSc
         RT_STAMP_AT(st1);
         if (live) h = nearest_any<kSrc, kCount>(sc, v, r, &w);
         RT_STAMP_AT(st2);
-        finish_nearest<kCam, kFresnel, kAa, kSky>(sc, fp, b, v.sph, k, live, r, sig, p, h, ql.count, obase, rbase);
+        finish_nearest<kCam, kFresnel, kAa, kSky, kMom>(sc, fp, b, v.sph, k, live, r, sig, p, h, ql.count, obase, rbase);
         RT_STAMP_AT(st3);
 #if RT_STAMP
         acc[1] += st1 - st0; acc[2] += st2 - st1; acc[3] += st3 - st2; acc[4] += 1;
@@ -275,17 +276,17 @@ hipError_t launch_nearest_src(const DevScene& sc, const FrameParams& fp, const W
     const size_t lds = staged_bytes<kSrc>(sc) + queue_lds_bytes(b.G);
     const bool cam = k == 0;
     return dispatch_bools(
-        [&](auto kCam, auto kCount, auto kFresnel, auto kAa, auto kSky) {
-            // kAa exists only with kCam, and a camera-grid source only as the camera pass
-            if constexpr (!kCam() && (kAa() || Src<kSrc>::cgrid)) {
+        [&](auto kCam, auto kCount, auto kFresnel, auto kAa, auto kSky, auto kMom) {
+            // kAa exists only with kCam, kMom only with kAa, and a camera-grid source only as the camera pass
+            if constexpr ((!kCam() && (kAa() || Src<kSrc>::cgrid)) || (kMom() && !kAa())) {
                 return hipErrorInvalidValue;
             } else {
-                hipLaunchKernelGGL((wf_nearest<kSrc, kCam(), kCount(), kFresnel(), kAa(), kSky()>), dim3(b.G), dim3(kWfThreads),
-                                   lds, s, sc, fp, b, k);
+                hipLaunchKernelGGL((wf_nearest<kSrc, kCam(), kCount(), kFresnel(), kAa(), kSky(), kMom()>), dim3(b.G),
+                                   dim3(kWfThreads), lds, s, sc, fp, b, k);
                 return hipSuccess;
             }
         },
-        cam, count, sc.has_fresnel, cam && fp.aa_acc, sc.skybox);
+        cam, count, sc.has_fresnel, cam && fp.aa_acc, sc.skybox, cam && aa_moments(fp));
 }
 
 }  // namespace rtamd

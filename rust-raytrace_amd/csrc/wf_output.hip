@@ -18,7 +18,7 @@ namespace {
 // (csky) is finished here, in row order: the ray rebuilt from the FRAME coordinates (camera_ray:
 // tile origin, bands, the pass's AA sample), the skybox sampled, and the pixel written as the
 // average of its spp identical samples (main.rs:47-56) or, kAa, the sample added to its running sum.
-template <bool kAa>
+template <bool kAa, bool kMom = false>
 __global__ __launch_bounds__(kWfThreads) void wf_sky_pixels(DevScene sc, FrameParams fp, WfBufs b) {
     __shared__ double s_srgb[255];
     for (int i = threadIdx.x; i < 255; i += kWfThreads) s_srgb[i] = c_srgb_avg[i];
@@ -29,7 +29,7 @@ __global__ __launch_bounds__(kWfThreads) void wf_sky_pixels(DevScene sc, FramePa
         if (!b.csky()[p]) continue;
         const uint32_t lx = static_cast<uint32_t>(p % fp.tile_w), lrow = fp.row0 + static_cast<uint32_t>(p / fp.tile_w);
         const Col c = background(sc, camera_ray(sc, fp, lx, lrow, fp.aa_pass));
-        if constexpr (kAa) aa_add(fp, static_cast<uint32_t>(p), aa_sample(c));
+        if constexpr (kAa) aa_add<kMom>(fp, static_cast<uint32_t>(p), aa_sample(c));
         else write_pixel(fp, lx, lrow, average_samples(c, fp.spp), s_srgb);
     }
 }
@@ -101,7 +101,7 @@ __global__ __launch_bounds__(kWfThreads) void wf_compose(DevScene sc, FrameParam
 // running sums.  Row by row, 64 consecutive pixels per wave: the pass's sample colour of each
 // pixel from the pixel map (the background's, an ambient end's, or the chain's, which the fold
 // left in term[chain]) is added to the pixel's running sum (aa_add: coalesced).
-template <bool kSky>
+template <bool kSky, bool kMom = false>
 __global__ __launch_bounds__(kWfThreads) void wf_aa_compose(DevScene sc, FrameParams fp, WfBufs b) {
     const uint32_t lane = threadIdx.x & 63u;
     RT_FOR_ROW_SEGMENTS(fp, lrow, x0) {
@@ -114,7 +114,7 @@ __global__ __launch_bounds__(kWfThreads) void wf_aa_compose(DevScene sc, FramePa
         else if (code == kPixBackground) s = Col{fp.aa_bg[0], fp.aa_bg[1], fp.aa_bg[2]};
         else if (code & kPixAmbient) s = aa_sample(end_colour(sc, static_cast<int32_t>(code & ~kPixAmbient)));
         else s = Col{ldn(&b.term(0)[code]), ldn(&b.term(1)[code]), ldn(&b.term(2)[code])};
-        aa_add(fp, p, s);
+        aa_add<kMom>(fp, p, s);
     }
 }
 
@@ -145,6 +145,63 @@ __global__ __launch_bounds__(kWfThreads) void accum_resolve(FrameParams fp, cons
         }
         store_row_segment(fp, s_rgb[wave], s_bgr[wave], dw, lrow, x0, nv, r, g, bl, q);
     }
+}
+
+// rt_accum_noise: the estimate of a moments accumulator.  sums: the tile's 3 f64 sums per
+// pixel, then, as a plane of their own, its 3 f64 sums of squares per pixel; n = samples >= 2.  Per pixel and
+// channel, every line one IEEE f64 operation (no fma): mean = S / N; d = Q - (S * mean); v = d < 0 ? 0 : d /
+// (N * (N - 1)) (a NaN d stays NaN); err = sqrt((v_r + v_g) + v_b) / (floor + ((|mean_r| + |mean_g|) +
+// |mean_b|)); above = !(err <= threshold).  Row by row, 64 consecutive pixels per wave as accum_resolve reads
+// them; variance (3 f32 per pixel, staged through the wave's LDS slice: consecutive dwords) and error (1 f32 per
+// pixel) may be null.  A wave counts its pixels above by ballot and adds its total once to *above, which the host
+// zeroed on the stream.  Reads the sums and squares, never writes them.
+__global__ __launch_bounds__(kWfThreads) void accum_noise(FrameParams fp, const double* sums, uint32_t samples, double err_floor,
+                                                          double threshold, float* variance, float* error,
+                                                          unsigned long long* above) {
+    __shared__ float s_var[kComposeWaves][192];
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+    const double* squares = sums + 3 * (static_cast<size_t>(fp.tile_w) * fp.tile_h);
+    const double N = static_cast<double>(samples), den = __dmul_rn(N, N - 1.0);
+    unsigned long long count = 0;
+    RT_FOR_ROW_SEGMENTS(fp, lrow, x0) {
+        const uint32_t nv = min(64u, fp.tile_w - x0);
+        const size_t p0 = static_cast<size_t>(lrow) * fp.tile_w + x0;
+        float vf[3] = {0.0f, 0.0f, 0.0f}, ef = 0.0f;
+        bool over = false;
+        if (lane < nv) {
+            const double* a = sums + 3 * (p0 + lane);
+            const double* q = squares + 3 * (p0 + lane);
+            double v[3], mean[3];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                const double S = ldn(&a[k]), Q = ldn(&q[k]);
+                mean[k] = S / N;
+                const double d = __dsub_rn(Q, __dmul_rn(S, mean[k]));
+                v[k] = d < 0.0 ? 0.0 : d / den;
+                vf[k] = static_cast<float>(v[k]);
+            }
+            const double err = sqrt(__dadd_rn(__dadd_rn(v[0], v[1]), v[2])) /
+                               __dadd_rn(err_floor, __dadd_rn(__dadd_rn(fabs(mean[0]), fabs(mean[1])), fabs(mean[2])));
+            ef = static_cast<float>(err);
+            over = !(err <= threshold);
+        }
+        count += static_cast<unsigned long long>(__popcll(__ballot(over)));
+        if (variance) {
+            float* s = s_var[wave];
+            s[3 * lane] = vf[0]; s[3 * lane + 1] = vf[1]; s[3 * lane + 2] = vf[2];
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            float* dst = variance + 3 * p0;
+#pragma unroll
+            for (uint32_t j = 0; j < 3; ++j) {
+                const uint32_t i = lane + 64u * j;
+                if (i < 3 * nv) dst[i] = s[i];
+            }
+            __builtin_amdgcn_wave_barrier();
+        }
+        if (error && lane < nv) error[p0 + lane] = ef;
+    }
+    if (lane == 0 && count) atomicAdd(above, count);
 }
 
 // Sparse host copies (rt_render, tuning sparse_out): after the
@@ -274,11 +331,15 @@ hipError_t launch_sky_pixels(const DevScene& sc, const FrameParams& fp, const Wf
     const uint64_t npix = static_cast<uint64_t>(fp.tile_w) * fp.rows;
     const dim3 grid(std::max(1u, static_cast<uint32_t>(std::min<uint64_t>(4u * b.G, (npix + kWfThreads - 1) / kWfThreads))));
     (void)dispatch_bools(
-        [&](auto kAa) {
-            hipLaunchKernelGGL(wf_sky_pixels<kAa()>, grid, dim3(kWfThreads), 0, s, sc, fp, b);
-            return hipSuccess;
+        [&](auto kAa, auto kMom) {
+            if constexpr (kMom() && !kAa()) {                  // (kMom: a moments accumulator's passes only)
+                return hipErrorInvalidValue;
+            } else {
+                hipLaunchKernelGGL((wf_sky_pixels<kAa(), kMom()>), grid, dim3(kWfThreads), 0, s, sc, fp, b);
+                return hipSuccess;
+            }
         },
-        fp.aa_acc != nullptr);
+        fp.aa_acc != nullptr, aa_moments(fp));
     return m ? m->mark(s, kKfCompose) : hipGetLastError();
 }
 
@@ -287,17 +348,25 @@ hipError_t launch_sky_pixels(const DevScene& sc, const FrameParams& fp, const Wf
 hipError_t launch_compose(const DevScene& sc, const FrameParams& fp, const WfBufs& b, hipStream_t s) {
     const dim3 grid = row_grid(fp, 4u * b.G);
     return dispatch_bools(
-        [&](auto kAa, auto kSky) {
-            if constexpr (kAa()) hipLaunchKernelGGL(wf_aa_compose<kSky()>, grid, dim3(kWfThreads), 0, s, sc, fp, b);
+        [&](auto kAa, auto kSky, auto kMom) {
+            if constexpr (kAa()) hipLaunchKernelGGL((wf_aa_compose<kSky(), kMom()>), grid, dim3(kWfThreads), 0, s, sc, fp, b);
             else hipLaunchKernelGGL(wf_compose<kSky()>, grid, dim3(kWfThreads), 0, s, sc, fp, b);
             return hipSuccess;
         },
-        fp.aa_acc != nullptr, sc.skybox);
+        fp.aa_acc != nullptr, sc.skybox, aa_moments(fp));
 }
 
 hipError_t launch_accum_resolve(const FrameParams& fp, uint32_t workgroups, hipStream_t s) {
     if (fp.tile_w == 0 || fp.rows == 0) return hipSuccess;
     hipLaunchKernelGGL(accum_resolve, row_grid(fp, workgroups), dim3(kWfThreads), 0, s, fp, fp.aa_acc, fp.aa_spp);
+    return hipGetLastError();
+}
+
+hipError_t launch_accum_noise(const FrameParams& fp, uint32_t workgroups, double err_floor, double threshold, float* variance,
+                              float* error, unsigned long long* above, hipStream_t s) {
+    if (fp.tile_w == 0 || fp.rows == 0) return hipSuccess;
+    hipLaunchKernelGGL(accum_noise, row_grid(fp, workgroups), dim3(kWfThreads), 0, s, fp, fp.aa_acc, fp.aa_spp, err_floor, threshold,
+                       variance, error, above);
     return hipGetLastError();
 }
 

@@ -75,7 +75,7 @@ __device__ __forceinline__ Col tail_chain(const DevScene& sc, const FrameParams&
 // record loads and level stores stay coalesced.  gridDim.x workgroups, all
 // resident; workgroup w publishes its counts in region w and zeros in the
 // other regions r = w (mod gridDim.x) of every generation >= T.
-template <bool kFresnel, bool kCount, bool kAa = false, bool kSky = false, bool kPack = false>
+template <bool kFresnel, bool kCount, bool kAa = false, bool kSky = false, bool kPack = false, bool kMom = false>
 __global__ __launch_bounds__(kWfThreads, 4) void wf_tail(DevScene sc, FrameParams fp, WfBufs b, int T, int W) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     __shared__ uint32_t s_cnt[2][kMaxGenerations];
@@ -102,7 +102,7 @@ __global__ __launch_bounds__(kWfThreads, 4) void wf_tail(DevScene sc, FrameParam
         const Col term = tail_chain<kFresnel, kCount, kSky, kPack>(sc, fp, b, v, T - 1, in, nlev, s_cnt, wn, wsh);
         const Col folded = fold_levels<kFresnel, kPack>(sc, b, in.c, nlev, term);
         const Col res = kAa ? aa_sample(folded) : average_samples(folded, fp.spp);
-        emit_chain<kAa>(fp, b, in.c, b.compose ? 0u : b.cpix()[in.c], res, s_srgb);
+        emit_chain<kAa, kMom>(fp, b, in.c, b.compose ? 0u : b.cpix()[in.c], res, s_srgb);
     }
     __syncthreads();
     for (uint32_t rg = blockIdx.x; rg < b.G; rg += gridDim.x) {
@@ -123,12 +123,16 @@ hipError_t launch_tail(const DevScene& sc, const FrameParams& fp, const WfBufs& 
                        int width, hipStream_t s) {
     const size_t lds = staged_bytes<kSrcBvhL8C>(sc) + queue_lds_bytes(b.G);
     return dispatch_bools(
-        [&](auto kFresnel, auto kCount, auto kAa, auto kSky, auto kPack) {
-            hipLaunchKernelGGL((wf_tail<kFresnel(), kCount(), kAa(), kSky(), kPack()>), dim3(wgs), dim3(kWfThreads), lds, s, sc,
-                               fp, b, T, width);
-            return hipSuccess;
+        [&](auto kFresnel, auto kCount, auto kAa, auto kSky, auto kPack, auto kMom) {
+            if constexpr (kMom() && !kAa()) {                  // (kMom: a moments accumulator's passes only)
+                return hipErrorInvalidValue;
+            } else {
+                hipLaunchKernelGGL((wf_tail<kFresnel(), kCount(), kAa(), kSky(), kPack(), kMom()>), dim3(wgs), dim3(kWfThreads),
+                                   lds, s, sc, fp, b, T, width);
+                return hipSuccess;
+            }
         },
-        sc.has_fresnel, count, fp.aa_acc != nullptr, sc.skybox, packed);
+        sc.has_fresnel, count, fp.aa_acc != nullptr, sc.skybox, packed, aa_moments(fp));
 }
 
 RT_UNIT_WARM(wf_tail)

@@ -175,6 +175,18 @@ def _load():
                                           C.c_size_t]),
         "rt_checkpoint_read": (C.c_int, [C.c_char_p, P(rt_render_opts), P(C.c_uint64), P(C.c_uint32), P(C.c_double),
                                          C.c_size_t]),
+        "rt_accum_create_moments": (C.c_int, [C.c_void_p, P(rt_render_opts), P(C.c_void_p)]),
+        "rt_accum_has_moments": (C.c_int, [C.c_void_p, P(C.c_int32)]),
+        "rt_accum_download_moments": (C.c_int, [C.c_void_p, C.c_void_p, P(C.c_double), C.c_size_t]),
+        "rt_accum_upload_moments": (C.c_int, [C.c_void_p, C.c_void_p, P(C.c_double), P(C.c_double), C.c_size_t, C.c_uint32]),
+        "rt_accum_noise": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.c_void_p, P(C.c_uint64),
+                                     C.c_void_p]),
+        "rt_accum_noise_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_double, P(C.c_float), P(C.c_float),
+                                          P(C.c_uint64)]),
+        "rt_checkpoint_write_moments": (C.c_int, [C.c_char_p, P(rt_render_opts), C.c_uint64, C.c_uint32, P(C.c_double),
+                                                  P(C.c_double), C.c_size_t]),
+        "rt_checkpoint_read_moments": (C.c_int, [C.c_char_p, P(rt_render_opts), P(C.c_uint64), P(C.c_uint32), P(C.c_double),
+                                                 P(C.c_double), C.c_size_t]),
         "rt_ctx_generation_counts": (C.c_int, [C.c_void_p, P(C.c_uint32), P(C.c_uint32), C.c_int]),
         "rt_ctx_kernel_times": (C.c_int, [C.c_void_p, P(C.c_double), P(C.c_uint32), C.c_int]),
         "rt_light_grid_candidates": (C.c_int, [C.c_void_p, C.c_int, C.c_int, P(C.c_double), C.c_uint32,
@@ -740,10 +752,11 @@ class Context:
                 "c": od[:, 12], "p": od[:, 13], "col": od[:, 14:17], "pow": od[:, 17], "sin": od[:, 18],
                 "cos": od[:, 19], "has_range": oi[:, 0] != 0, "diffuse": oi[:, 1] != 0, "specular": oi[:, 2] != 0}
 
-    def accumulator(self, opts):
+    def accumulator(self, opts, moments=False):
         """rt_accum_create: a progressive render of opts' tile (main.rs:47-56 split over calls), bound to
-        opts' image-defining fields and to the scene uploaded now."""
-        return Accumulator(self, opts)
+        opts' image-defining fields and to the scene uploaded now.  moments: rt_accum_create_moments, an
+        accumulator that also keeps every pixel's sums of squares (Accumulator.noise)."""
+        return Accumulator(self, opts, moments)
 
     def kernel_times(self):
         """{family: (summed ms, launches)} over the RT_TIME_KERNELS renders since
@@ -778,10 +791,11 @@ class Accumulator:
     image of the samples so far (sum / samples), as often as wanted.  Close it before its Context, or
     after (then only close() does anything)."""
 
-    def __init__(self, ctx, opts):
+    def __init__(self, ctx, opts, moments=False):
         self._ctx = ctx
         h = C.c_void_p()
-        _check(lib.rt_accum_create(ctx._h, C.byref(opts), C.byref(h)), ctx._h)
+        create = lib.rt_accum_create_moments if moments else lib.rt_accum_create
+        _check(create(ctx._h, C.byref(opts), C.byref(h)), ctx._h)
         self._h = h
         self.tile_w, self.tile_h = opts.tile_w, opts.tile_h
 
@@ -827,6 +841,47 @@ class Accumulator:
         _check(lib.rt_accum_upload(self._ctx._h, self._h, arr.ctypes.data_as(C.POINTER(C.c_double)), arr.size, int(samples)),
                self._ctx._h)
 
+    @property
+    def has_moments(self):
+        f = C.c_int32()
+        _check(lib.rt_accum_has_moments(self._h, C.byref(f)))
+        return bool(f.value)
+
+    def download_moments(self, cap=None):
+        """rt_accum_download_moments -> squares float64 [tile_h, tile_w, 3]; cap: the capacity passed (a test's)."""
+        sq = np.zeros((self.tile_h, self.tile_w, 3), np.float64)
+        _check(lib.rt_accum_download_moments(self._ctx._h, self._h, sq.ctypes.data_as(C.POINTER(C.c_double)),
+                                             sq.size if cap is None else int(cap)), self._ctx._h)
+        return sq
+
+    def upload_moments(self, sums, squares, samples):
+        s = np.ascontiguousarray(sums, dtype=np.float64)
+        q = np.ascontiguousarray(squares, dtype=np.float64)
+        if s.size != q.size:
+            raise ValueError("sums and squares differ in size")
+        PD = C.POINTER(C.c_double)
+        _check(lib.rt_accum_upload_moments(self._ctx._h, self._h, s.ctypes.data_as(PD), q.ctypes.data_as(PD), s.size,
+                                           int(samples)), self._ctx._h)
+
+    def noise(self, floor, threshold, variance=True, error=True):
+        """rt_accum_noise_host -> (variance float32 [tile_h, tile_w, 3] or None, error float32 [tile_h, tile_w]
+        or None, above): the variance of the mean, the relative error and the pixels with !(err <= threshold)."""
+        var = np.zeros((self.tile_h, self.tile_w, 3), np.float32) if variance else None
+        err = np.zeros((self.tile_h, self.tile_w), np.float32) if error else None
+        above = C.c_uint64()
+        PF = C.POINTER(C.c_float)
+        _check(lib.rt_accum_noise_host(self._ctx._h, self._h, float(floor), float(threshold),
+                                       var.ctypes.data_as(PF) if variance else None,
+                                       err.ctypes.data_as(PF) if error else None, C.byref(above)), self._ctx._h)
+        return var, err, above.value
+
+    def noise_device(self, floor, threshold, d_variance_ptr=None, d_error_ptr=None, stream_ptr=None):
+        """rt_accum_noise into device buffers (raw pointers, either may be None) -> above."""
+        above = C.c_uint64()
+        _check(lib.rt_accum_noise(self._ctx._h, self._h, float(floor), float(threshold), C.c_void_p(d_variance_ptr or 0),
+                                  C.c_void_p(d_error_ptr or 0), C.byref(above), C.c_void_p(stream_ptr or 0)), self._ctx._h)
+        return above.value
+
     def close(self):
         if self._h:
             lib.rt_accum_destroy(self._h)
@@ -863,6 +918,32 @@ def checkpoint_read(path, header_only=False):
     _check(lib.rt_checkpoint_read(os.fsencode(path), C.byref(o), C.byref(h), C.byref(n),
                                   sums.ctypes.data_as(C.POINTER(C.c_double)), sums.size))
     return o, h.value, n.value, sums
+
+
+def checkpoint_write_moments(path, opts, scene_hash, samples, sums, squares):
+    """rt_checkpoint_write_moments (host only): a format version 2 file, the sums and then the squares."""
+    s = np.ascontiguousarray(sums, dtype=np.float64)
+    q = np.ascontiguousarray(squares, dtype=np.float64)
+    if s.size != q.size:
+        raise ValueError("sums and squares differ in size")
+    PD = C.POINTER(C.c_double)
+    _check(lib.rt_checkpoint_write_moments(os.fsencode(path), C.byref(opts), int(scene_hash), int(samples),
+                                           s.ctypes.data_as(PD), q.ctypes.data_as(PD), s.size))
+
+
+def checkpoint_read_moments(path, header_only=False):
+    """rt_checkpoint_read_moments -> (opts, scene_hash, samples, sums, squares), float64 [tile_h, tile_w, 3] or None."""
+    o = rt_render_opts()
+    h, n = C.c_uint64(), C.c_uint32()
+    _check(lib.rt_checkpoint_read_moments(os.fsencode(path), C.byref(o), C.byref(h), C.byref(n), None, None, 0))
+    if header_only:
+        return o, h.value, n.value, None, None
+    sums = np.zeros((o.tile_h, o.tile_w, 3), np.float64)
+    sq = np.zeros((o.tile_h, o.tile_w, 3), np.float64)
+    PD = C.POINTER(C.c_double)
+    _check(lib.rt_checkpoint_read_moments(os.fsencode(path), C.byref(o), C.byref(h), C.byref(n), sums.ctypes.data_as(PD),
+                                          sq.ctypes.data_as(PD), sums.size))
+    return o, h.value, n.value, sums, sq
 
 
 def scene_hash(text):
