@@ -74,6 +74,8 @@ extern "C" {
  * Still 10: second moments (rt_accum_create_moments, rt_accum_has_moments, rt_accum_download_moments /
  * upload_moments, rt_accum_noise / noise_host, rt_checkpoint_write_moments / read_moments) add functions only:
  * no struct, enum or tuning key; accum_noise is timed under RT_KF_COMPOSE.
+ * Still 10: the variance-guided denoiser (rt_denoise_variance, rt_denoise_var and rt_denoise_var_device) adds two
+ * functions and one struct; rt_denoise_params, rt_denoise_inputs and rt_denoise_flags are as they were, no tuning key.
  * 9: first-hit feature buffers: enum rt_aov, rt_aov_buffers, rt_render_aov and rt_render_aov_device
  * (depth, normal, albedo, coverage and object id of the camera rays' first hits).  Functions and types
  * added only: no struct, enum value or tuning key changed, RT_KF_COUNT is still 8.
@@ -525,6 +527,53 @@ int rt_denoise_device(rt_ctx* ctx, const rt_denoise_params* params, const rt_den
 /* Synchronous, HOST buffers: device buffers allocated, filled, filtered, copied back and freed.  No performance claim. */
 int rt_denoise(rt_ctx* ctx, const rt_denoise_params* params, const rt_denoise_inputs* host, float* out_rgb,
                uint8_t* out_bgr);
+/* ---- denoiser, variance-guided: a colour weight scaled by the pixel's own noise (SVGF, Schied et al. 2017) ----
+ * What a caller with a moments accumulator does: rt_accum_noise gives the variance of every pixel's mean, and the
+ * filter then tells a colour edge that is signal (a shadow edge, a texture, a reflection: no normal or depth edge)
+ * from one that is noise, pixel by pixel, where RT_DN_COLOR has one global sigma_color.
+ *
+ * The rule.  Every rule of rt_denoise above holds unchanged (f64, never fused, the written order, every f32 read
+ * widened first); only the following is added.
+ * Inputs: variance [h, w, 3] f32, tight, exactly what rt_accum_noise writes; sigma_variance and variance_floor.
+ * Pack, per pixel p, one scalar variance: per channel k, u_k = (double)variance[3p+k]; with RT_DN_DEMODULATE and
+ *   a_k > 0.0: u_k = u_k / (a_k*a_k); then u_k = u_k > 0.0 ? u_k : 0.0 (a NaN, a negative value and -0.0 become
+ *   +0.0).  var_p = (float)((u_r + u_g) + u_b).
+ * Pass i at pixel p, before the taps: gs = 0, gw = 0; for dy = -1 .. 1 (outer), dx = -1 .. 1 (inner), q = p + (dx, dy)
+ *   (always one pixel apart, not the pass's step; a q outside the image is skipped):
+ *     gk = G[|dy|] * G[|dx|], G = {1/2, 1/4};  gs = gs + gk*var_q;  gw = gw + gk
+ *   g = gs / gw;  den = (sigma_variance*sigma_variance)*g + variance_floor;  vs = 0.
+ *   any tap but the centre, after the RT_DN_COLOR step if that flag is set and before the skip test (unchanged):
+ *     e = (dr*dr + dg*dg) + db*db as RT_DN_COLOR forms it (this pass's input colours);  wt = wt / (1.0 + e/den)
+ *   a kept tap, the centre included: vs = vs + (wt*wt)*var_q.
+ *   After the taps: x = vs / (wsum*wsum);  x = x > 0.0 ? x : 0.0.  Between passes (float)x is the pixel's variance,
+ *   as the f32 colour is its colour.
+ * After the last pass out_variance [h, w] f32 (optional) = (float)x.  With RT_DN_DEMODULATE it is in the units of
+ *   the demodulated signal: it is not multiplied back by the albedo.
+ * No sqrt, no exp: e and the variance are both colour squared.
+ * What follows from it: every stored variance lies in [0, +inf] (never NaN, never negative).  With variance 2^100
+ *   everywhere and colours of ordinary magnitude e/den < 2^-53, every new divisor is exactly 1.0, and out_rgb and
+ *   out_bgr are rt_denoise's bit for bit under every flag mask.  A constant dyadic image is still a fixed point
+ *   for any variance, and a non-finite colour pixel still keeps to itself.  With variance 0 everywhere a tap
+ *   across a colour step e carries at most kw * variance_floor / e.
+ *
+ * Ordering, scratch (the same images: the variance rides in the colour record's fourth float, so the size is
+ *   unchanged) and "not a render" are as for rt_denoise; a call is ordered after the context's previous denoise
+ *   of either kind.
+ * RT_E_INVALID, before anything changes: every refusal of rt_denoise in its order, with "all three outputs NULL"
+ *   (out_rgb, out_bgr, out_variance) in the place of "both outputs NULL"; then a NULL rt_denoise_variance; a NULL
+ *   variance; a sigma_variance or a variance_floor that is not finite and > 0; out_variance == variance. */
+typedef struct {
+    const float* variance;      /* [h, w, 3]: the variance of the mean, per channel (rt_accum_noise) */
+    float* out_variance;        /* [h, w] or NULL: the filtered scalar variance */
+    double sigma_variance;
+    double variance_floor;
+} rt_denoise_variance;
+/* Asynchronous on `stream` (NULL: the context's own), DEVICE buffers; any output may be NULL, not all three. */
+int rt_denoise_var_device(rt_ctx* ctx, const rt_denoise_params* params, const rt_denoise_inputs* dev,
+                          const rt_denoise_variance* dev_var, float* d_out_rgb, uint8_t* d_out_bgr, void* stream);
+/* Synchronous, HOST buffers, as rt_denoise.  No performance claim. */
+int rt_denoise_var(rt_ctx* ctx, const rt_denoise_params* params, const rt_denoise_inputs* host,
+                   const rt_denoise_variance* host_var, float* out_rgb, uint8_t* out_bgr);
 /* ---- progressive rendering (main.rs:47-56 split over calls) ----
  * The reference's pixel is `res = BLACK; for _ in 0..antialias { res = res + raytrace(..) }; res / antialias`
  * (main.rs:47-56).  An rt_accum keeps `res` of every pixel of one tile on the device between calls: f64

@@ -171,7 +171,8 @@ hipError_t launch_query_occluded(const DevScene& sc, unsigned long long* counter
                                  uint32_t n, uint8_t* occluded, int src, uint32_t workgroups, hipStream_t s);
 
 // The denoiser (wf_denoise.hip, rt_denoise_device; the rule: include/raytrace_amd.h).  Device images of w x h
-// pixels.  DnRec: one 16-byte record per pixel, a colour (r, g, b, unused) or a guide (normal x, y, z, depth).
+// pixels.  DnRec: one 16-byte record per pixel, a colour (r, g, b, and the variance-guided forms' variance, else 0)
+// or a guide (normal x, y, z, depth).
 struct alignas(16) DnRec {
     float x, y, z, w;
 };
@@ -180,19 +181,27 @@ struct DnFilter {
     uint32_t flags, squarings;      // rt_denoise_flags, rt_denoise_params::normal_squarings
     double sigma_color, sigma_depth;
 };
+// The variance-guided forms (rt_denoise_var_device): the colour record's fourth float carries the pixel's scalar
+// variance from pass to pass; out_variance (w x h floats, may be null) is what the last pass leaves of it.
+struct DnVar {
+    double sigma_variance, variance_floor;
+    float* out_variance;
+};
 // The pack pass: the caller's tight f32 images (normal / depth null where their flag is off: zeros; albedo read under
-// RT_DN_DEMODULATE only) into one colour and one guide record per pixel.
+// RT_DN_DEMODULATE only) into one colour and one guide record per pixel.  variance (w x h x 3 floats) non-null: the
+// variance-guided form, which also packs the scalar variance.
 hipError_t launch_denoise_pack(const DnFilter& f, const float* rgb, const float* normal, const float* depth,
-                               const float* albedo, DnRec* colour, DnRec* guide, hipStream_t s);
+                               const float* albedo, DnRec* colour, DnRec* guide, hipStream_t s, const float* variance = nullptr);
 // One filter pass of step `step` from `src` into `dst`; lds: the tile-staging form (step <= kDnLdsMaxStep only,
-// else hipErrorInvalidValue).  grid: the plan's (one workgroup per kDnTileW x kDnTileH tile).
+// else hipErrorInvalidValue).  grid: the plan's (one workgroup per kDnTileW x kDnTileH tile).  var non-null: the
+// variance-guided form.
 hipError_t launch_denoise_pass(const DnFilter& f, uint32_t step, bool lds, const DnRec* src, const DnRec* guide, DnRec* dst,
-                               uint32_t grid_x, uint32_t grid_y, hipStream_t s);
+                               uint32_t grid_x, uint32_t grid_y, hipStream_t s, const DnVar* var = nullptr);
 // The last pass: as above, then remodulated by `albedo` (RT_DN_DEMODULATE) and written as f32 (out_rgb, tight; may be
 // null) and sRGB B G R bytes (out_bgr, rows of bgr_pitch bytes, padding left alone; may be null).
 hipError_t launch_denoise_last(const DnFilter& f, uint32_t step, bool lds, const DnRec* src, const DnRec* guide,
                                const float* albedo, float* out_rgb, uint8_t* out_bgr, uint32_t bgr_pitch, uint32_t grid_x,
-                               uint32_t grid_y, hipStream_t s);
+                               uint32_t grid_y, hipStream_t s, const DnVar* var = nullptr);
 
 // The general path (path_kernel.hip): every material / light / camera class,
 // keyed random draws, one work-item per pixel over the HBM recursion stack.

@@ -13,12 +13,22 @@
 //            [--progressive K] [--checkpoint FILE] [--aov PREFIX]
 //            [--until-noise T] [--noise-floor F] [--noise-pixels P] [--variance FILE.pfm]
 //            [--denoise ITER] [--denoise-flags normal,depth,color,demodulate|none]
+//            [--denoise-variance SIGMA] [--denoise-variance-floor F]
 //
 // --denoise ITER: the image goes through the edge-avoiding a-trous filter (rt_denoise, ITER passes 1..8) before it is
 // written: the frame is rendered with its f32 colours, the first-hit feature buffers with the same --spp, --jitter
 // and --seed (rt_render_aov), and the BMP holds the filter's bytes.  --denoise-flags (default normal,depth) names the
 // guides; normal_squarings 5, sigma_depth 0.05, sigma_color 1.0.  With --progressive every written frame is
 // denoised.  Single-device; a DepthOfFieldCamera has no feature buffers and is refused.
+// --denoise ITER --denoise-variance SIGMA [--denoise-variance-floor F]: the variance-guided filter (rt_denoise_var,
+// sigma_variance SIGMA, variance_floor F, default 2^-20).  The frame is rendered through an accumulator that keeps the
+// sums of squares (without --progressive: one rt_render_accumulate call, whose image is the one-shot render's bit
+// for bit), rt_accum_noise gives the variance of every pixel's mean (--noise-floor applies), and that guides the
+// filter beside the feature buffers.  With --progressive every written frame of at least 2 samples goes through it; a
+// frame of 1 sample has no variance, goes through the plain filter and says so on stderr.  Needs --jitter random
+// and --spp of at least 2.  --until-noise, --variance and --checkpoint combine with it: they read the same
+// accumulator (the stop rule is asked on the unfiltered samples; --variance writes the image the filter was guided by),
+// and a --noise-floor that is not finite and > 0 is refused as it is for them.
 // --aov PREFIX: instead of the image, the first-hit feature buffers of the frame (rt_render_aov; --spp, --jitter,
 // --seed, --width, --height apply) as PFM files (portable float map: "PF" 3 channels / "Pf" 1 channel, width
 // height, scale -1.0 = little-endian, rows bottom-up, which is the library's row order): PREFIX.depth.pfm,
@@ -69,11 +79,13 @@ struct Args {
     double noise_floor = 1e-3;
     long noise_pixels = 0;
     std::string variance;              // --variance FILE.pfm
-    bool moments() const { return until_noise != 0 || !variance.empty(); }
+    bool moments() const { return until_noise != 0 || !variance.empty() || denoise_var; }
     std::string aov;                   // --aov PREFIX: write the feature buffers instead of the image
     long denoise = 0;                  // --denoise ITER: filter passes (0: off)
     unsigned denoise_flags = RT_DN_NORMAL | RT_DN_DEPTH;
     bool bad_denoise_flags = false;
+    bool denoise_var = false;          // --denoise-variance SIGMA: the variance-guided filter
+    double sigma_variance = 0, variance_floor = 1.0 / 1048576.0;
 };
 
 // "normal,depth,color,demodulate" (any subset, any order) or "none" -> rt_denoise_flags; false: an unknown word.
@@ -115,6 +127,8 @@ bool parse_args(int argc, char** argv, Args& a) {
         else if (k == "--aov" && (v = val())) a.aov = v;
         else if (k == "--denoise" && (v = val())) a.denoise = std::atol(v);
         else if (k == "--denoise-flags" && (v = val())) a.bad_denoise_flags = !parse_denoise_flags(v, a.denoise_flags);
+        else if (k == "--denoise-variance" && (v = val())) { a.denoise_var = true; a.sigma_variance = std::atof(v); }
+        else if (k == "--denoise-variance-floor" && (v = val())) a.variance_floor = std::atof(v);
         else if (k == "--jitter" && (v = val())) a.jitter = std::string(v) == "center" ? RT_JITTER_CENTER : RT_JITTER_RANDOM;
         else if (k == "--algo" && (v = val())) {
             std::string s = v;
@@ -127,7 +141,8 @@ bool parse_args(int argc, char** argv, Args& a) {
                                  "                [--seed N] [--algo auto|wavefront|wavefront-aa|path|lds|global]\n"
                                  "                [--progressive K] [--checkpoint FILE] [--aov PREFIX]\n"
                                  "                [--until-noise T] [--noise-floor F] [--noise-pixels P] [--variance FILE.pfm]\n"
-                                 "                [--denoise ITER] [--denoise-flags normal,depth,color,demodulate|none]\n");
+                                 "                [--denoise ITER] [--denoise-flags normal,depth,color,demodulate|none]\n"
+                                 "                [--denoise-variance SIGMA] [--denoise-variance-floor F]\n");
             return false;
         }
     }
@@ -161,6 +176,12 @@ struct Denoiser {
     bool run(rt_ctx* ctx, const float* rgb, uint8_t* frame) const {
         const rt_denoise_inputs in{rgb, normal.data(), depth.data(), albedo.data()};
         return rt_denoise(ctx, &p, &in, nullptr, frame) == RT_OK;
+    }
+    // --denoise-variance: the same with the variance of the mean (tight f32, 3 channels) as one more guide
+    bool run_var(rt_ctx* ctx, const Args& a, const float* rgb, const float* variance, uint8_t* frame) const {
+        const rt_denoise_inputs in{rgb, normal.data(), depth.data(), albedo.data()};
+        const rt_denoise_variance var{variance, nullptr, a.sigma_variance, a.variance_floor};
+        return rt_denoise_var(ctx, &p, &in, &var, nullptr, frame) == RT_OK;
     }
 };
 
@@ -198,8 +219,8 @@ int run_denoised(const Args& a, rt_scene* scene, uint32_t W, uint32_t H, uint32_
 
 bool write_pfm(const std::string& path, uint32_t W, uint32_t H, int channels, const float* data);
 
-// --progressive / --checkpoint / --until-noise / --variance: one device, the whole frame in one accumulator,
-// `total` samples in steps.
+// --progressive / --checkpoint / --until-noise / --variance / --denoise-variance: one device, the whole frame in one
+// accumulator, `total` samples in steps (without --progressive: one step).
 int run_progressive(const Args& a, rt_scene* scene, const std::string& text, uint32_t W, uint32_t H, uint32_t total) {
     uint32_t pitch = 0;
     uint8_t hdr[122];
@@ -266,13 +287,26 @@ int run_progressive(const Args& a, rt_scene* scene, const std::string& text, uin
         }
     }
     Denoiser dn;                       // --denoise: the guides once, at the frame's sample count
-    std::vector<float> rgb;
+    std::vector<float> rgb, dn_var;
     if (a.denoise > 0) {
         if (!dn.setup(ctx, a, W, H, total, pitch)) { std::printf("error: --denoise: %s\n", rt_last_error(ctx)); return done_with(2); }
         rgb.resize(n_doubles);
+        if (a.denoise_var) dn_var.resize(n_doubles);
     }
     const uint32_t step = a.progressive > 0 ? static_cast<uint32_t>(std::min<long>(a.progressive, total)) : total;
     std::vector<uint8_t> frame(static_cast<size_t>(pitch) * H, 0);
+    // --denoise: the image of the `have` samples so far through the filter; variance-guided from 2 samples on
+    auto denoised = [&](uint32_t have) {
+        if (rt_accum_resolve_host(ctx, acc, pitch, rgb.data(), nullptr) != RT_OK) return false;
+        if (!a.denoise_var) return dn.run(ctx, rgb.data(), frame.data());
+        if (have < 2) {
+            std::fprintf(stderr, "samples %u: no variance yet, the plain filter\n", have);
+            return dn.run(ctx, rgb.data(), frame.data());
+        }
+        uint64_t above = 0;
+        return rt_accum_noise_host(ctx, acc, a.noise_floor, 1.0, dn_var.data(), nullptr, &above) == RT_OK &&
+               dn.run_var(ctx, a, rgb.data(), dn_var.data(), frame.data());
+    };
     const std::string tmp = a.out + ".tmp";
     uint64_t rays = 0;
     double kms = 0;
@@ -303,8 +337,7 @@ int run_progressive(const Args& a, rt_scene* scene, const std::string& text, uin
         kms += st.kernel_ms;
         if (done == 0) break;
         // the image of the samples so far, under a temporary name first: --out is always a whole image
-        if (a.denoise > 0 ? rt_accum_resolve_host(ctx, acc, pitch, rgb.data(), nullptr) != RT_OK || !dn.run(ctx, rgb.data(), frame.data())
-                          : rt_accum_resolve_host(ctx, acc, pitch, nullptr, frame.data()) != RT_OK) {
+        if (a.denoise > 0 ? !denoised(done) : rt_accum_resolve_host(ctx, acc, pitch, nullptr, frame.data()) != RT_OK) {
             std::printf("error: %s\n", rt_last_error(ctx));
             return done_with(1);
         }
@@ -411,6 +444,18 @@ int main(int argc, char** argv) {
     int ndev = 0;
     rt_device_count(&ndev);
     if (ndev < 1) { std::printf("error: no GPU\n"); return 1; }
+    if (a.denoise_var) {
+        if (a.denoise == 0) { std::printf("error: --denoise-variance guides the filter of --denoise ITER: name the passes\n"); return 2; }
+        if (!(a.sigma_variance > 0) || !std::isfinite(a.sigma_variance) || !(a.variance_floor > 0) || !std::isfinite(a.variance_floor)) {
+            std::printf("error: --denoise-variance and --denoise-variance-floor take finite values > 0\n");
+            return 2;
+        }
+        if (a.jitter != RT_JITTER_RANDOM) {
+            std::printf("error: --denoise-variance needs --jitter random (samples through one point have no variance)\n");
+            return 2;
+        }
+        if (spp < 2) { std::printf("error: --denoise-variance needs --spp of at least 2 (a variance of 2 samples)\n"); return 2; }
+    }
     if (a.denoise != 0 || a.bad_denoise_flags) {
         if (a.bad_denoise_flags) {
             std::printf("error: --denoise-flags takes normal, depth, color, demodulate (comma-separated) or none\n");

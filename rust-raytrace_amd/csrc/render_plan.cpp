@@ -317,28 +317,57 @@ int plan_query_args(const QueryArgs& a, const char** err) {
 
 uint32_t plan_query_workgroups(uint64_t n, int n_cu) { return plan_aov_workgroups(n, n_cu); }
 
-int plan_denoise_args(const rt_denoise_params* p, const rt_denoise_inputs* in, const void* out_rgb, const void* out_bgr,
-                      const char** err) {
+namespace {
+
+bool dn_sigma_ok(double v) { return std::isfinite(v) && v > 0.0; }
+
+// The checks rt_denoise and rt_denoise_var share, each text under the name of the entry point that was called.
+// out_var: rt_denoise_var's third output (null for rt_denoise, and for a null rt_denoise_variance).
+#define DN_TEXT(text) (var_call ? "rt_denoise_var: " text : "rt_denoise: " text)
+int denoise_args(bool var_call, const rt_denoise_params* p, const rt_denoise_inputs* in, const void* out_rgb, const void* out_bgr,
+                 const void* out_var, const char** err) {
     auto refuse = [&](const char* why) {
         *err = why;
         return RT_E_INVALID;
     };
-    auto sigma_ok = [](double v) { return std::isfinite(v) && v > 0.0; };
-    if (!p || !in) return refuse("rt_denoise: null argument");
-    if (p->width == 0 || p->height == 0) return refuse("rt_denoise: width and height must be > 0");
-    if (p->iterations < 1 || p->iterations > kDnMaxIterations) return refuse("rt_denoise: iterations must be 1..8");
-    if (p->flags & ~kDnAllFlags) return refuse("rt_denoise: unknown flag bits");
-    if (p->normal_squarings > kDnMaxSquarings) return refuse("rt_denoise: normal_squarings must be 0..10");
-    if (p->variant > 2) return refuse("rt_denoise: variant must be 0, 1 or 2");
-    if (!in->rgb) return refuse("rt_denoise: the rgb input is NULL");
+    if (!p || !in) return refuse(DN_TEXT("null argument"));
+    if (p->width == 0 || p->height == 0) return refuse(DN_TEXT("width and height must be > 0"));
+    if (p->iterations < 1 || p->iterations > kDnMaxIterations) return refuse(DN_TEXT("iterations must be 1..8"));
+    if (p->flags & ~kDnAllFlags) return refuse(DN_TEXT("unknown flag bits"));
+    if (p->normal_squarings > kDnMaxSquarings) return refuse(DN_TEXT("normal_squarings must be 0..10"));
+    if (p->variant > 2) return refuse(DN_TEXT("variant must be 0, 1 or 2"));
+    if (!in->rgb) return refuse(DN_TEXT("the rgb input is NULL"));
     if (((p->flags & RT_DN_NORMAL) && !in->normal) || ((p->flags & RT_DN_DEPTH) && !in->depth) ||
         ((p->flags & RT_DN_DEMODULATE) && !in->albedo))
-        return refuse("rt_denoise: a selected guide's buffer is NULL");
-    if ((p->flags & RT_DN_DEPTH) && !sigma_ok(p->sigma_depth)) return refuse("rt_denoise: sigma_depth must be finite and > 0");
-    if ((p->flags & RT_DN_COLOR) && !sigma_ok(p->sigma_color)) return refuse("rt_denoise: sigma_color must be finite and > 0");
-    if (!out_rgb && !out_bgr) return refuse("rt_denoise: both outputs are NULL");
-    if (p->bgr_pitch != 0 && p->bgr_pitch / 3 < p->width) return refuse("rt_denoise: bgr_pitch is below 3 * width");
-    if (out_rgb == static_cast<const void*>(in->rgb)) return refuse("rt_denoise: out_rgb must not be the rgb input");
+        return refuse(DN_TEXT("a selected guide's buffer is NULL"));
+    if ((p->flags & RT_DN_DEPTH) && !dn_sigma_ok(p->sigma_depth)) return refuse(DN_TEXT("sigma_depth must be finite and > 0"));
+    if ((p->flags & RT_DN_COLOR) && !dn_sigma_ok(p->sigma_color)) return refuse(DN_TEXT("sigma_color must be finite and > 0"));
+    if (!out_rgb && !out_bgr && !out_var) return refuse(var_call ? "rt_denoise_var: all three outputs are NULL" : "rt_denoise: both outputs are NULL");
+    if (p->bgr_pitch != 0 && p->bgr_pitch / 3 < p->width) return refuse(DN_TEXT("bgr_pitch is below 3 * width"));
+    if (out_rgb == static_cast<const void*>(in->rgb)) return refuse(DN_TEXT("out_rgb must not be the rgb input"));
+    return RT_OK;
+}
+#undef DN_TEXT
+
+}  // namespace
+
+int plan_denoise_args(const rt_denoise_params* p, const rt_denoise_inputs* in, const void* out_rgb, const void* out_bgr,
+                      const char** err) {
+    return denoise_args(false, p, in, out_rgb, out_bgr, nullptr, err);
+}
+
+int plan_denoise_var_args(const rt_denoise_params* p, const rt_denoise_inputs* in, const rt_denoise_variance* var,
+                          const void* out_rgb, const void* out_bgr, const char** err) {
+    auto refuse = [&](const char* why) {
+        *err = why;
+        return RT_E_INVALID;
+    };
+    if (const int rc = denoise_args(true, p, in, out_rgb, out_bgr, var ? var->out_variance : nullptr, err); rc != RT_OK) return rc;
+    if (!var) return refuse("rt_denoise_var: the rt_denoise_variance struct is NULL");
+    if (!var->variance) return refuse("rt_denoise_var: the variance input is NULL");
+    if (!dn_sigma_ok(var->sigma_variance)) return refuse("rt_denoise_var: sigma_variance must be finite and > 0");
+    if (!dn_sigma_ok(var->variance_floor)) return refuse("rt_denoise_var: variance_floor must be finite and > 0");
+    if (var->out_variance == var->variance) return refuse("rt_denoise_var: out_variance must not be the variance input");
     return RT_OK;
 }
 

@@ -171,6 +171,11 @@ constexpr uint32_t kDnAllFlags = RT_DN_NORMAL | RT_DN_DEPTH | RT_DN_COLOR | RT_D
 constexpr uint32_t kDnMaxIterations = 8, kDnMaxSquarings = 10;
 int plan_denoise_args(const rt_denoise_params* p, const rt_denoise_inputs* in, const void* out_rgb, const void* out_bgr,
                       const char** err);
+// rt_denoise_var / rt_denoise_var_device: the checks above in their order, with "all three outputs NULL" (out_rgb,
+// out_bgr, var->out_variance) where they have "both outputs NULL", then those of the rt_denoise_variance struct
+// (null: refused).  The passes are plan_denoise's: the variance rides in the colour record, the scratch is the same.
+int plan_denoise_var_args(const rt_denoise_params* p, const rt_denoise_inputs* in, const rt_denoise_variance* var,
+                          const void* out_rgb, const void* out_bgr, const char** err);
 // The passes of a checked call.  Pass i has step 2^i.  A pass whose step is 1 or 2 has the LDS form (wf_denoise.hip
 // stages the workgroup's kDnTileW x kDnTileH tile and a halo of 2 * step pixels, which fits its static LDS up to
 // step kDnLdsMaxStep); every later pass reads its taps through L2.  variant 1: every pass direct; 2: LDS where it

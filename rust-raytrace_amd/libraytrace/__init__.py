@@ -119,6 +119,11 @@ class rt_denoise_inputs(C.Structure):
     _fields_ = [("rgb", C.c_void_p), ("normal", C.c_void_p), ("depth", C.c_void_p), ("albedo", C.c_void_p)]
 
 
+class rt_denoise_variance(C.Structure):
+    _fields_ = [("variance", C.c_void_p), ("out_variance", C.c_void_p), ("sigma_variance", C.c_double),
+                ("variance_floor", C.c_double)]
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise ImportError(f"{LIB_PATH} is missing: run `make -C rust-raytrace_amd` "
@@ -162,6 +167,10 @@ def _load():
         "rt_denoise": (C.c_int, [C.c_void_p, P(rt_denoise_params), P(rt_denoise_inputs), C.c_void_p, C.c_void_p]),
         "rt_denoise_device": (C.c_int, [C.c_void_p, P(rt_denoise_params), P(rt_denoise_inputs), C.c_void_p, C.c_void_p,
                                         C.c_void_p]),
+        "rt_denoise_var": (C.c_int, [C.c_void_p, P(rt_denoise_params), P(rt_denoise_inputs), P(rt_denoise_variance),
+                                     C.c_void_p, C.c_void_p]),
+        "rt_denoise_var_device": (C.c_int, [C.c_void_p, P(rt_denoise_params), P(rt_denoise_inputs), P(rt_denoise_variance),
+                                            C.c_void_p, C.c_void_p, C.c_void_p]),
         "rt_accum_create": (C.c_int, [C.c_void_p, P(rt_render_opts), P(C.c_void_p)]),
         "rt_accum_destroy": (None, [C.c_void_p]),
         "rt_accum_samples": (C.c_int, [C.c_void_p, P(C.c_uint32)]),
@@ -652,6 +661,49 @@ class Context:
             setattr(ins, name, ptr or None)
         _check(lib.rt_denoise_device(self._h, C.byref(params), C.byref(ins), C.c_void_p(d_out_rgb_ptr or 0),
                                      C.c_void_p(d_out_bgr_ptr or 0), C.c_void_p(stream_ptr or 0)), self._h)
+
+    def denoise_var(self, rgb, variance, guides=None, sigma_variance=2.0, variance_floor=2.0 ** -20, variance_out=False,
+                    rgb_out=True, bgr_out=True, **params):
+        """rt_denoise_var: the variance-guided filter on host arrays (synchronous) -> (rgb, bgr, variance float32 [h, w]
+        or None), rgb and bgr as denoise gives them.  variance: float32 [h, w, 3], the variance of the mean
+        (Accumulator.noise); guides and params as for denoise."""
+        rgb = np.ascontiguousarray(rgb, dtype=np.float32)
+        h, w = rgb.shape[:2]
+        p = denoise_params(w, h, **params)
+        variance = np.ascontiguousarray(variance, dtype=np.float32)
+        assert variance.size == h * w * 3, "variance"
+        keep = [rgb, variance]
+        ins = rt_denoise_inputs(rgb=rgb.ctypes.data)
+        for name, a in (guides or {}).items():
+            if name not in ("normal", "depth", "albedo"):
+                raise TypeError(f"unknown guide {name}")
+            a = np.ascontiguousarray(a, dtype=np.float32)
+            assert a.size == h * w * (1 if name == "depth" else 3), name
+            keep.append(a)
+            setattr(ins, name, a.ctypes.data)
+        pitch = p.bgr_pitch or 3 * w
+        out_rgb = np.zeros((h, w, 3), np.float32) if rgb_out else None
+        out_bgr = np.full((h, pitch), 0xCD, np.uint8) if bgr_out else None
+        out_var = np.zeros((h, w), np.float32) if variance_out else None
+        var = rt_denoise_variance(variance=variance.ctypes.data, out_variance=out_var.ctypes.data if variance_out else None,
+                                  sigma_variance=sigma_variance, variance_floor=variance_floor)
+        _check(lib.rt_denoise_var(self._h, C.byref(p), C.byref(ins), C.byref(var), out_rgb.ctypes.data if rgb_out else None,
+                                  out_bgr.ctypes.data if bgr_out else None), self._h)
+        return out_rgb, out_bgr, out_var
+
+    def denoise_var_device(self, params, d_rgb_ptr, d_variance_ptr, guide_ptrs, d_out_rgb_ptr, d_out_bgr_ptr, d_out_variance_ptr=None,
+                           sigma_variance=2.0, variance_floor=2.0 ** -20, stream_ptr=None):
+        """rt_denoise_var_device: asynchronous, on device buffers (raw pointers), as denoise_device; d_variance_ptr:
+        [h, w, 3] floats (Accumulator.noise_device writes them), d_out_variance_ptr: [h, w] floats or None."""
+        ins = rt_denoise_inputs(rgb=d_rgb_ptr or None)
+        for name, ptr in (guide_ptrs or {}).items():
+            if name not in ("normal", "depth", "albedo"):
+                raise TypeError(f"unknown guide {name}")
+            setattr(ins, name, ptr or None)
+        var = rt_denoise_variance(variance=d_variance_ptr or None, out_variance=d_out_variance_ptr or None,
+                                  sigma_variance=sigma_variance, variance_floor=variance_floor)
+        _check(lib.rt_denoise_var_device(self._h, C.byref(params), C.byref(ins), C.byref(var), C.c_void_p(d_out_rgb_ptr or 0),
+                                         C.c_void_p(d_out_bgr_ptr or 0), C.c_void_p(stream_ptr or 0)), self._h)
 
     def reserve(self, opts, host=False, stream_ptr=None):
         """rt_ctx_reserve: allocate and warm up everything a render with opts needs (host: rt_render's

@@ -8,7 +8,7 @@ Each input is the stderr of
 on one checkout: the remark logs of all its translation units, one after the other (the parser
 goes line by line; a checkout from before the split has trace_kernel.hip and path_kernel.hip).  Kernels are matched
 by demangled name (c++filt); a trailing `false` template argument of wf_nearest / wf_fold / wf_tail / wf_shade /
-trace_frame_kernel / wf_compose / wf_aa_compose in the second build (a parameter the first build
+trace_frame_kernel / wf_compose / wf_aa_compose / dn_pack / dn_pass in the second build (a parameter the first build
 does not have; a kernel the first build has as a plain function loses its `<false>`) is dropped
 before matching.  Prints every kernel of the first build whose
 VGPRs, AGPRs, scratch, LDS or occupancy differ in the second (exit status 1 if any), then the
@@ -46,7 +46,7 @@ def parse(path):
 
 
 def first_build_name(n):
-    m = re.match(r"(wf_nearest|wf_fold|wf_tail|wf_shade|trace_frame_kernel|wf_compose|wf_aa_compose)<(.*)>$", n)
+    m = re.match(r"(wf_nearest|wf_fold|wf_tail|wf_shade|trace_frame_kernel|wf_compose|wf_aa_compose|dn_pack|dn_pass)<(.*)>$", n)
     if not m:
         return n
     args = [a.strip() for a in m.group(2).split(",")]
